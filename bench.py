@@ -9,8 +9,14 @@ the reference's GI mode, svotrace.comp:443-560) go through the HIP path, pool re
 Rays = intersectOctree-equivalent casts actually performed (untimed counting pass of the first and
 the last timed frame); value = rays of all ranks / wall time of K steps.
 
-After the timed region the frames still held by the ring (the last `inflight` timed frames, as
-rendered with that many launches in flight) are read back and a pixel subsample of each is compared
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what that figure needs and no more: scene, counting
+passes, warm-up, the K timed steps, the line.  --dump-outputs DIR also writes the frame of the last timed step as
+.npy files (the same arguments give the same frame, bit for bit, so two builds can be compared).  Everything else
+below -- the check against the oracle, the longer region, the legs through the JNI-typed calls, the CPU baseline --
+runs with --full, or when its own option names it.
+
+With --full (or --verify 1), after the timed region the frames still held by the ring (the last `inflight` timed
+frames, as rendered with that many launches in flight) are read back and a pixel subsample of each is compared
 bit-for-bit with the CPU oracle: the line carries "verified": true, or the run exits non-zero.
 
 N > 1: `python bench.py --gpus N` starts N ranks itself (a child torch.distributed.run, before this
@@ -30,7 +36,7 @@ a partial batch if need be.  `--inflight 1 --batch 1` is the reference's own loo
 Presets: --config C2 | C3 (default, the metric) | C4 | C5 are BASELINE.json's configs.
 Also on the JSON line: roofline (algorithmic bytes / HIP-event kernel time vs 8 TB/s HBM, plus the
 instruction-issue figures that actually bind, from the committed PMC passes when they were taken on
-exactly these kernel sources) and cpu_baseline (the CPU oracle on a bounded subsample).
+exactly these kernel sources) and, with --full, cpu_baseline (the CPU oracle on a bounded subsample).
 """
 import argparse
 import hashlib
@@ -62,6 +68,9 @@ VALU_CYCLES = (42 * 2.35 + 34 * 4.3) / 76.0
 # whole region is submitted at once and ends in ONE tail.
 DEFAULT_BATCH = {1: 4, 2: 4, 4: 4, 8: 4}
 DEFAULT_INFLIGHT = 6
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # --dump-outputs: all files of one dump together
+# the legs behind the headline and what --full sets each to; without --full they are off unless named (parse)
+FULL_LEGS = dict(moving=1, long_steps=400, default_abi=1, cpu_seconds=15.0, verify=1, isolated=1)
 
 PRESETS = {
     # name: size, width, height, mode, bounces (path segments), mirror mask, spp
@@ -84,6 +93,18 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs behind the headline, each of which can still be switched by its own option: the check of the "
+                         "ring's frames against the CPU oracle (--verify), the longer timed region (--long-steps), the moving camera "
+                         "(--moving), the JNI-typed run, the reference's loop and the three cameras (--default-abi, --ref-loop, "
+                         "--by-camera), single frames with the GPU to themselves (--isolated) and the CPU baseline (--cpu-seconds).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints its line; a leg named by its own option "
+                         "runs either way")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left in its ring slot -- the frame a host reads back -- "
+                         "as DIR/rgba.npy and DIR/depth.npy in float32 (and, with --hits 1, DIR/hits.npy in float64: a hit record's words "
+                         "do not fit a float32); frames too large for %d MB in all are cut to a fixed, seeded sample of pixels, whose "
+                         "indices go to DIR/pixel_index.npy" % (DUMP_LIMIT_BYTES // 10 ** 6))
     ap.add_argument("--config", choices=sorted(PRESETS), default=None, help="BASELINE.json config preset (default: C3)")
     ap.add_argument("--size", type=int, default=None, help="SVO resolution N (N^3 voxels)")
     ap.add_argument("--width", type=int, default=None)
@@ -113,10 +134,10 @@ def parse(argv=None):
     ap.add_argument("--camera-path", choices=["static", "orbit"], default="static",
                     help="orbit: every timed frame carries its own camera (Camera.rotate + strafe through the host mirror) and "
                          "frameNumber 1 (Main resets it on motion, Main.java:225-233, 275): svo_ring_submit_cams")
-    ap.add_argument("--moving", type=int, default=1, help="also measure the default configuration with a moving camera "
+    ap.add_argument("--moving", type=int, default=None, help="(default: 1 with --full, else 0) also measure the default configuration with a moving camera "
                                                           "(value_moving_camera; one GPU, static runs only)")
-    ap.add_argument("--long-steps", type=int, default=400, help="steps of the second, longer timed region (value_long_run; 0 = skip)")
-    ap.add_argument("--default-abi", type=int, default=1, help="also run the configuration through JNI-typed calls only, with no tuning / "
+    ap.add_argument("--long-steps", type=int, default=None, help="(default: 400 with --full, else 0) steps of the second, longer timed region (value_long_run; 0 = skip)")
+    ap.add_argument("--default-abi", type=int, default=None, help="(default: 1 with --full, else 0) also run the configuration through JNI-typed calls only, with no tuning / "
                                                                 "pipeline call (value_default_abi; one GPU, default config only)")
     ap.add_argument("--fallback", type=int, default=1, help="N > 1 without a launcher: when a rung (driver / exchange) fails, times out or "
                                                             "does not verify, go on with the next one in a fresh child process")
@@ -140,10 +161,10 @@ def parse(argv=None):
     ap.add_argument("--waves", type=int, default=-1, help="persistent waves per CU and launch (svo_set_tuning); -1 = no call: the library's "
                                                           "own choice (10 for a ring of several slots, fill the GPU otherwise)")
     ap.add_argument("--thresh", type=int, default=-1, help="refill round threshold in sixteenths (svo_set_tuning); -1 = no call: the library's 9")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-oracle sample time (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="(default: 15 with --full, else 0) target CPU-oracle sample time (0 = skip)")
     ap.add_argument("--hits", type=int, default=0, help="also store 16-byte hit records per pixel")
-    ap.add_argument("--verify", type=int, default=1, help="check the ring's frames against the CPU oracle after timing")
-    ap.add_argument("--isolated", type=int, default=1, help="also time single frames with the GPU to themselves (kernel_ms_isolated); "
+    ap.add_argument("--verify", type=int, default=None, help="(default: 1 with --full, else 0) check the ring's frames against the CPU oracle after timing")
+    ap.add_argument("--isolated", type=int, default=None, help="(default: 1 with --full, else 0) also time single frames with the GPU to themselves (kernel_ms_isolated); "
                                                           "0 in PMC passes, so that every launch of the kernel is a timed-region launch")
     ap.add_argument("--beam", type=int, default=0, help="useBeamOptimization (coarse depth pre-pass, Main.java:257-266)")
     ap.add_argument("--comm-cus", type=int, default=-1, help="CUs per XCD the render streams leave free for the collective's kernels "
@@ -155,6 +176,9 @@ def parse(argv=None):
     ap.add_argument("--as-rank", default=None, help="r/n: render what rank r of n would, on one GPU, no communication")
     args = ap.parse_args(argv)
     args.exchange_given = args.exchange is not None
+    for leg, on in FULL_LEGS.items():
+        if getattr(args, leg) is None:
+            setattr(args, leg, on if args.full else 0)
     for leg in ("ref_loop", "by_camera"):      # the legs behind the headline go together unless named
         if getattr(args, leg) is None:
             setattr(args, leg, args.default_abi)
@@ -328,6 +352,31 @@ def default_batch(args, world):
     if args.spp > 1 or args.seq > 1:
         return 1
     return DEFAULT_BATCH.get(world, 4 if world > 8 else 1)
+
+
+def dump_outputs(out_dir, images):
+    """--dump-outputs: the frame a host reads back from the ring -- images = (frameNumber, colour [H][W] rgba8 words, depth
+    [H][W] float32[, hit records [H][W][4] int32]) as FrameRing.frame_images returns them -- as <out_dir>/rgba.npy [..., 4]
+    and depth.npy in float32, hits.npy [..., 4] in float64.  A frame that does not fit DUMP_LIMIT_BYTES is cut to the same
+    seeded sample of pixels on every run; pixel_index.npy then holds their row-major indices (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    col = np.ascontiguousarray(images[1].cpu().numpy())
+    h, w = col.shape
+    out = {"rgba": col.view(np.uint8).reshape(h * w, 4).astype(np.float32),
+           "depth": images[2].cpu().numpy().reshape(h * w).astype(np.float32)}
+    if len(images) > 3:
+        out["hits"] = images[3].cpu().numpy().reshape(h * w, 4).astype(np.float64)
+    per_px = sum(a.dtype.itemsize * (a.size // (h * w)) for a in out.values())
+    if per_px * h * w + 1024 * len(out) <= DUMP_LIMIT_BYTES:
+        out = {k: a.reshape((h, w) + a.shape[1:]) for k, a in out.items()}
+    else:
+        keep = (DUMP_LIMIT_BYTES - 1024 * (len(out) + 1)) // (per_px + 8)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=keep, replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["pixel_index"] = idx.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def pmc_key(args, width, height, nbuf, batch):
@@ -636,7 +685,7 @@ def probe_command(args, exchange):
     """A rank of the small run that tries an exchange out: 512^3, 640x360, 12 frames, verified against the oracle on rank 0."""
     return [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--size", "512", "--width", "640", "--height", "360",
             "--steps", "8", "--warmup", "4", "--inflight", "3", "--batch", "2", "--cpu-seconds", "0", "--moving", "0", "--default-abi", "0",
-            "--long-steps", "0", "--isolated", "0", "--probe", "0", "--driver", "torch", "--exchange", exchange]
+            "--long-steps", "0", "--isolated", "0", "--verify", "1", "--probe", "0", "--driver", "torch", "--exchange", exchange]
 
 
 def probe_env(exchange, attempt, port=None):
@@ -900,6 +949,11 @@ def main(argv=None, ctx_factory=None):
         dist.all_gather(tall, torch.tensor([elapsed], dtype=torch.float64, device=dev))
         rank_ms = [float(t.item()) / args.steps * 1e3 for t in tall]
         elapsed = max(float(t.item()) for t in tall)
+    if args.dump_outputs:
+        ring.drain()      # before any later region renders over the slots
+        if rank == 0:
+            b = (ring.dispatches - 1) % nbuf      # the slot of the last submission; the last step is its last frame
+            dump_outputs(args.dump_outputs, ring.frame_images(b, ring.count_of[b] - 1))
     # A driver's 20-step region is 11 ms at N = 1 and 1.5 ms of work per rank at N = 8 -- all start and drain, and millisecond
     # stalls of a box do not average out.  The same protocol again over a longer region, as an extra key.
     long_run = None

@@ -106,7 +106,7 @@ def _worker(rank, world, port, argv, out_path):
 
 
 ARGS = ["--size", "64", "--width", "72", "--height", "50", "--steps", "5", "--warmup", "2", "--inflight", "2", "--batch", "2",
-        "--cpu-seconds", "0", "--long-steps", "6"]
+        "--full", "--cpu-seconds", "0", "--long-steps", "6"]
 
 
 @pytest.mark.parametrize("world,scaling", [(2, "strong"), (2, "weak"), (3, "strong")])
@@ -151,3 +151,74 @@ def test_bench_main_one_rank_stub(tmp_path):
     assert rc == 0 and line["verified"] is True and line["ranks_seen"] == 1 and line["gather_ms"] is None
     # (value_one_frame_at_a_time is the wall clock of the reference's loop through JNI-typed calls: GPU only)
     assert line["kernel_rate_isolated"] > 0 and line["value_one_frame_at_a_time"] is None and line["comm_cus_per_xcd"] == 0
+
+
+PLAIN = ["--size", "64", "--width", "72", "--height", "50", "--steps", "5", "--warmup", "2", "--inflight", "2", "--batch", "2", "--gpus", "1"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_last_frame(tmp_path):
+    """without --full: no leg behind the headline runs (no check against the oracle, no longer region, no isolated frames, no
+    CPU baseline), the line still carries the headline's keys; --dump-outputs writes the frame of the LAST timed step
+    (frameNumber 2 + warm-up + steps - 1) as float32 arrays, the same bytes on every run"""
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        os.environ.pop(k, None)
+    import bench
+    from oracle import oracle
+    import svo_raytracer_amd.scene as scene
+    from svo_raytracer_amd.cameras import CAMERAS
+    dumps = []
+    for d in ("a", "b"):
+        rc, line = bench.main(PLAIN + ["--dump-outputs", str(tmp_path / d)], ctx_factory=StubContext)
+        assert rc == 0 and line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert (line["unit"], line["higher_is_better"], line["dtype"]) == ("Mrays/s", True, "f32") and line["metric"].startswith("Mrays/s")
+        assert line["verified"] is None and line["config"]["verification"] is None and line["cpu_baseline"] is None
+        assert line["value_long_run"] is None and line["kernel_rate_isolated"] is None and line["roofline"]["kernel_ms_isolated"] is None
+        assert line["moving_camera"] is None and line["default_abi"] is None and line["reference_loop"] is None and line["by_camera"] is None
+        assert sorted(os.listdir(tmp_path / d)) == ["depth.npy", "rgba.npy"]
+        dumps.append({k: np.load(tmp_path / d / (k + ".npy")) for k in ("rgba", "depth")})
+    ref = oracle.render(scene.build_scene(64)[0], 72, 50, CAMERAS["K1"], 2 + 2 + 5 - 1, 0, want_hits=False)
+    for z in dumps:
+        assert z["rgba"].dtype == np.float32 and z["rgba"].shape == (50, 72, 4) and (z["rgba"] == ref["rgba"]).all()
+        assert z["depth"].dtype == np.float32 and z["depth"].shape == (50, 72)
+        assert (z["depth"].view(np.uint32) == ref["depth"].view(np.uint32)).all()
+    assert all(dumps[0][k].tobytes() == dumps[1][k].tobytes() for k in dumps[0])
+
+
+def test_a_leg_named_by_its_own_option_runs_without_full_and_full_sets_the_defaults():
+    import bench
+    a = bench.parse([])
+    assert (a.full, a.verify, a.long_steps, a.moving, a.default_abi, a.ref_loop, a.by_camera, a.isolated, a.cpu_seconds) == (False, 0, 0, 0, 0, 0, 0, 0, 0)
+    a = bench.parse(["--full"])
+    assert (a.verify, a.long_steps, a.moving, a.default_abi, a.ref_loop, a.by_camera, a.isolated, a.cpu_seconds) == (1, 400, 1, 1, 1, 1, 1, 15.0)
+    a = bench.parse(["--verify", "1", "--long-steps", "7"])
+    assert (a.verify, a.long_steps, a.moving, a.cpu_seconds) == (1, 7, 0, 0)
+    a = bench.parse(["--full", "--verify", "0", "--default-abi", "0"])
+    assert (a.verify, a.default_abi, a.ref_loop, a.by_camera, a.moving) == (0, 0, 0, 0, 1)
+
+
+def test_dump_outputs_samples_a_frame_that_does_not_fit(tmp_path, monkeypatch):
+    """a frame larger than the limit is cut to a seeded sample of pixels: the same pixels every time, their indices written
+    next to them, everything together within the limit; hit records go out as float64 (a pointer does not fit a float32)"""
+    import torch
+    import bench
+    h, w = 37, 53
+    rng = np.random.default_rng(5)
+    col = rng.integers(-2 ** 31, 2 ** 31, size=(h, w), dtype=np.int64).astype(np.int32)
+    dep = rng.random((h, w), dtype=np.float32)
+    hits = rng.integers(0, 2 ** 31, size=(h, w, 4), dtype=np.int64).astype(np.int32)
+    images = (9, torch.from_numpy(col), torch.from_numpy(dep), torch.from_numpy(hits))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40000)      # the whole frame would take 37 * 53 * 52 = 101 972 bytes
+    out = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), images)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["depth.npy", "hits.npy", "pixel_index.npy", "rgba.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 40000
+        out.append({f[:-4]: np.load(tmp_path / d / f) for f in files})
+    z = out[0]
+    idx = z["pixel_index"].astype(np.int64)
+    assert z["pixel_index"].dtype == np.float64 and 500 < idx.size < h * w and (np.diff(idx) > 0).all() and idx[-1] < h * w
+    assert z["rgba"].dtype == np.float32 and (z["rgba"] == col.view(np.uint8).reshape(h * w, 4)[idx]).all()
+    assert z["depth"].dtype == np.float32 and (z["depth"] == dep.reshape(-1)[idx]).all()
+    assert z["hits"].dtype == np.float64 and (z["hits"] == hits.reshape(h * w, 4)[idx]).all()
+    assert all(out[0][k].tobytes() == out[1][k].tobytes() for k in z)

@@ -104,7 +104,7 @@ def test_bench_two_ranks_on_one_gpu_copy_exchange():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--exchange", "copy", "--size", "512",
            "--width", "640", "--height", "360", "--steps", "12", "--warmup", "4", "--inflight", "2", "--batch", "2", "--waves", "6",
-           "--cpu-seconds", "0", "--isolated", "0"]
+           "--full", "--cpu-seconds", "0", "--isolated", "0"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -122,7 +122,7 @@ def test_one_rank_under_the_launcher_reproduces_the_plain_run():
     """the driver starts N > 1 as `python -m torch.distributed.run ... bench.py --gpus N`; at N = 1 under that launcher the line
     must be the plain `bench.py --gpus 1` line: same workload, same ray count, verified, the value within a box's spread of a
     20-step region (both are all start and drain)"""
-    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--moving", "0", "--long-steps", "200"]
+    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0", "--moving", "0", "--long-steps", "200"]
     plain = _bench_line([sys.executable, os.path.join(ROOT, "bench.py")] + common)
     under = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                          "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + common)
@@ -146,7 +146,7 @@ def test_bench_group_driver_on_one_gpu(n):
     env = dict(os.environ, SVO_BENCH_ONE_GPU="1")
     line = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--driver", "group", "--exchange", "copy",
                         "--size", "512", "--width", "640", "--height", "360", "--steps", "12", "--warmup", "4", "--inflight", "3",
-                        "--batch", "2", "--waves", "6", "--long-steps", "24", "--cpu-seconds", "0"], env=env)
+                        "--batch", "2", "--waves", "6", "--full", "--long-steps", "24", "--cpu-seconds", "0"], env=env)
     assert line["verified"] is True and line["n_gpus"] == n and line["driver"].startswith("group")
     assert line["value"] > 0 and line["value_long_run"] > 0 and line["long_run_steps"] == 24
     assert "svo_group_" in line["config"]["workload"]
@@ -230,7 +230,7 @@ def test_ranks_under_the_launcher_negotiate_the_exchange_before_they_touch_the_g
     env.pop("SVO_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "512", "--width", "640",
-           "--height", "360", "--steps", "12", "--warmup", "4", "--inflight", "2", "--batch", "2", "--cpu-seconds", "0", "--isolated", "0",
+           "--height", "360", "--steps", "12", "--warmup", "4", "--inflight", "2", "--batch", "2", "--full", "--cpu-seconds", "0", "--isolated", "0",
            "--long-steps", "24", "--probe-timeout", "150"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]

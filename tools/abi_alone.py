@@ -8,7 +8,7 @@ import svo_raytracer_amd.scene as scene
 from svo_raytracer_amd import hiplib
 from svo_raytracer_amd.cameras import CAMERAS
 from svo_raytracer_amd.framering import FrameRing
-args = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--verify", "0"])
+args = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--verify", "0"])
 pool, _ = scene.build_scene(8192)
 RAYS = 3306337.0
 if os.environ.get("WHICH", "abi") == "abi":

@@ -3,7 +3,7 @@ O=gpurun_out/burst_ab.txt; : > $O
 for r in 1 2 3 4 5 6 7 8; do
   for a in "" "--waves 11" "--waves 12" "--waves 9"; do
     echo -n "[$a] " >> $O
-    timeout 600 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 --isolated 0 --moving 0 --default-abi 0 --long-steps 400 $a 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['value_long_run'], d['verified'])" >> $O 2>&1
+    timeout 600 python bench.py --steps 20 --warmup 5 --full --cpu-seconds 0 --isolated 0 --moving 0 --default-abi 0 --long-steps 400 $a 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['value_long_run'], d['verified'])" >> $O 2>&1
   done
 done
 python - <<PY

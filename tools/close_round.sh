@@ -18,9 +18,9 @@ if [ -f svo-raytracer_amd/csrc/libsvohip_stamps.so ]; then
   STAMPS_WAVES=10,24 STAMPS_BATCH=1 SVO_HIP_LIB=$GRAFT_REPO_ROOT/svo-raytracer_amd/csrc/libsvohip_stamps.so python tools/stamps.py >> $O/stamps.txt 2>&1
   cp gpurun_out/stamps_per_launch.json profiles/stamps_per_launch.json; tail -3 $O/stamps.txt | cut -c1-250
 fi
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | line > $O/bench_driver_k20.json
-B="--cpu-seconds 0 --moving 0 --default-abi 0 --long-steps 0"
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | line > $O/bench_driver_k20.json
+B="--full --cpu-seconds 0 --moving 0 --default-abi 0 --long-steps 0"
 V=$GRAFT_REPO_ROOT/svo-raytracer_amd/csrc/libsvohip_variants.so   # the comparators and the SVO_* switches live there
 python bench.py --inflight 1 --batch 1 $B 2>/dev/null | line > $O/bench_inflight1.json
 python bench.py --camera-path orbit $B 2>/dev/null | line > $O/bench_orbit.json

@@ -19,7 +19,7 @@ for rep in range(2):
             env["SVO_LOOP_WAVES"] = str(w)
         if ns:
             env["SVO_LOOP_SETS"] = str(ns)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "8", "--long-steps", "0", "--moving", "0",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "8", "--full", "--long-steps", "0", "--moving", "0",
                             "--default-abi", "0", "--by-camera", "0", "--ref-loop", "1", "--cpu-seconds", "0", "--isolated", "0"],
                            capture_output=True, env=env, cwd=ROOT)
         line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]

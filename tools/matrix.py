@@ -19,7 +19,7 @@ SCENE_TEXT = {"t1a8": "terrain, seed 1, amplitude 8/16 (rounds 1-5)", "t2a18": "
               "c1a8d64": "caves: terrain seed 1 + hashed balls (dens 64/256)",
               "d1a8x24": "dust: terrain seed 1 + floating particles (24/256 of the air cells)"}
 CAMS = ("K0", "K1", "K2")
-BENCH = ["--steps", "400", "--warmup", "24", "--long-steps", "0", "--moving", "0", "--default-abi", "0", "--by-camera", "0", "--ref-loop", "1", "--cpu-seconds", "0"]
+BENCH = ["--steps", "400", "--warmup", "24", "--full", "--long-steps", "0", "--moving", "0", "--default-abi", "0", "--by-camera", "0", "--ref-loop", "1", "--cpu-seconds", "0"]
 
 
 def bench_args(cell):

@@ -215,6 +215,11 @@ int svo_set_derived(svo_ctx *ctx, int mode);
 /* builds the table if the pool changed; *descriptors = its entries, *bytes = device memory it holds, *walkable = 1 if
  * pipeline 1 walks it (0 = the pool is not derivable), *build_ms = GPU time of the last build.  Any may be NULL. */
 int svo_derived_info(svo_ctx *ctx, uint64_t *descriptors, uint64_t *bytes, int *walkable, float *build_ms);
+/* reads the table out, for checking it: `count` 8-byte descriptors { first-child offset, child nibbles } to `desc` and
+ * `count` 8-byte entries { child-block base, tag mask | depth << 16 } to `aux` (host memory), from index `first`.  Builds
+ * the table first if the pool changed, like svo_derived_info, so this is the table the next dispatch walks: the one a
+ * ranged update was followed in, or a rebuilt one.  SVO_E_INVALID for a range past *descriptors.  Changes nothing. */
+int svo_derived_read(svo_ctx *ctx, uint64_t first, uint64_t count, void *desc, void *aux);
 /* svo_pool_update (Renderer.updateSSBO of an SDF brush stroke's two byte ranges, Main.java:349-350) does not drop a
  * walkable table: the states whose child block the range touches are recomputed, changed sibling groups and new
  * subtrees are appended at the table's end (SVO_DERIVED_REFRESH=0 in the environment: rebuild instead).  *refreshes =

@@ -603,6 +603,21 @@ int svo_derived_info(svo_ctx *c, uint64_t *descriptors, uint64_t *bytes, int *wa
   return SVO_OK;
 }
 
+int svo_derived_read(svo_ctx *c, uint64_t first, uint64_t count, void *desc, void *aux) {
+  if (!c) return SVO_E_INVALID;
+  if (!c->d_pool || c->pool_len < 7) return fail(c, SVO_E_NOPOOL, "svo_derived_read: no pool uploaded");
+  if (count && (!desc || !aux)) return fail(c, SVO_E_INVALID, "svo_derived_read: null buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = ensure_derived(c);
+  if (rc) return rc;
+  if (first > c->dt.count || count > c->dt.count - first) return fail(c, SVO_E_INVALID, "svo_derived_read: range past the table's end");
+  if (!count) return SVO_OK;
+  HIPCHK(c, hipDeviceSynchronize());   // (a refresh or a build has synchronised its stream; frames only read the table)
+  HIPCHK(c, hipMemcpy(desc, c->dt.desc + first, count * sizeof(uint2), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(aux, c->dt.aux + first, count * sizeof(uint2), hipMemcpyDeviceToHost));
+  return SVO_OK;
+}
+
 int svo_derived_refresh_info(svo_ctx *c, uint64_t *refreshes, uint64_t *states, uint64_t *added, float *gpu_ms) {
   if (!c) return SVO_E_INVALID;
   if (refreshes) *refreshes = c->dt.refreshes;

@@ -17,7 +17,7 @@ EXPORTS = [
     "svo_pool_reserve", "svo_pool_upload_device", "svo_pool_device_ptr", "svo_build_from_heightmap", "svo_build_from_voxels", "svo_bind_outputs", "svo_set_camera", "svo_set_params", "svo_resize", "svo_set_rows", "svo_set_stripes",
     "svo_set_pipeline", "svo_set_tuning", "svo_set_hit_records", "svo_set_progressive", "svo_set_batch", "svo_dispatch", "svo_dispatch_async", "svo_sync", "svo_set_pick", "svo_set_overlap", "svo_pick_info", "svo_count_frame",
     "svo_get_stats", "svo_set_stream", "svo_time_frames", "svo_read_color", "svo_read_depth", "svo_read_hits", "svo_read_pixel", "svo_read_beam",
-    "svo_output_device_ptrs", "svo_set_derived", "svo_derived_info", "svo_derived_refresh_info",
+    "svo_output_device_ptrs", "svo_set_derived", "svo_derived_info", "svo_derived_read", "svo_derived_refresh_info",
     "svo_ring_create", "svo_ring_destroy", "svo_ring_submit", "svo_ring_wait", "svo_ring_query", "svo_ring_read_color",
     "svo_ring_read_depth", "svo_ring_read_hits", "svo_ring_read_pixel", "svo_ring_bind_slot", "svo_ring_device_ptrs",
     "svo_set_reserved_cus", "svo_pool_commit", "svo_ring_forward_slot", "svo_dev_alloc", "svo_dev_free", "svo_dev_read",
@@ -114,6 +114,7 @@ def lib(path=None):
                                            ctypes.POINTER(u64), ctypes.POINTER(vp)]
         L.svo_set_derived.argtypes = [vp, ci]
         L.svo_derived_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci), fp]
+        L.svo_derived_read.argtypes = [vp, u64, u64, vp, vp]
         L.svo_derived_refresh_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), fp]
         L.svo_build_info.argtypes = []
         L.svo_dispatch.argtypes = [vp]
@@ -432,6 +433,15 @@ class HipContext:
         n, b, w, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int(), ctypes.c_float()
         self._chk(self._L.svo_derived_info(self._h, ctypes.byref(n), ctypes.byref(b), ctypes.byref(w), ctypes.byref(ms)))
         return {"descriptors": int(n.value), "bytes": int(b.value), "walkable": bool(w.value), "build_ms": float(ms.value)}
+
+    def derived_read(self, first=0, count=None):
+        """the table the next dispatch walks (built first if the pool changed), read out for checking: two uint32
+        (count, 2) arrays, desc = {first-child offset, child nibbles} and aux = {child-block base, tag mask | depth << 16}"""
+        if count is None:
+            count = self.derived_info()["descriptors"] - int(first)
+        desc, aux = np.empty((int(count), 2), np.uint32), np.empty((int(count), 2), np.uint32)
+        self._chk(self._L.svo_derived_read(self._h, int(first), int(count), desc.ctypes.data, aux.ctypes.data))
+        return desc, aux
 
     def derived_refresh_info(self):
         """what svo_pool_update did to the table: updates followed without a rebuild; states recomputed, descriptors appended

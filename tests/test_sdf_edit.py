@@ -113,11 +113,8 @@ def test_descriptor_table_follows_brush_strokes_without_a_rebuild():
     the oracle after every stroke, on the table, and the table must not have been rebuilt in between."""
     from svo_raytracer_amd import hiplib
     from oracle import oracle
-    n, lod = 128, 7
-    pool, _ = scene.build_scene(n)
-    o = hostlib.Octree(1 << 16)
-    o.adopt(pool)
-    rng = np.random.default_rng(11)
+    from derived_edits import brush_strokes
+    pool, _ = scene.build_scene(128)
     cams = [KEDIT, CAMERAS["K1"]]
     ctx = helpers.DualContext()
     try:
@@ -127,29 +124,17 @@ def test_descriptor_table_follows_brush_strokes_without_a_rebuild():
         info = ctx.derived_info()
         assert info["walkable"]
         followed = issued = 0
-        prev_host = pool
-        for stroke in range(14):
-            org = tuple(int(v) for v in rng.integers(n // 4, 3 * n // 4, 3))
-            r = int(rng.integers(3, 14))
-            val = int(rng.choice([0, 0, 1, 2, 3]))
-            if stroke % 5 == 4:
-                cb = restated.useSDFBrushBox(o, org, r, max(2, r // 2), r, val, worldSize=n, maxLOD=lod)
-            else:
-                cb = restated.useSDFBrushSphere(o, org, r, val, worldSize=n, maxLOD=lod)
-            host = o.getByteBuffer()
+        host = pool
+        for stroke, host, cb, root_changed in brush_strokes(pool, n=128, lod=7, strokes=14, seed=11):
             before = ctx.derived_refresh_info()["refreshes"]
-            # (a stroke that rewrites the root record -- its mask changes when one of the eight top-level children is
-            # re-tagged, common in a 128^3 world, out of reach of a brush at 8192^3 -- is the one case left to a rebuild)
-            root_changed = bool((host[1:7] != prev_host[1:7]).any())
             n_updates = 0
             if cb[1] > cb[0]:
                 ctx.pool_update(host, cb[0], cb[1]); n_updates += 1
             if cb[3] > cb[2]:
                 ctx.pool_update(host, cb[2], cb[3]); n_updates += 1
-            prev_host = host
             after = ctx.derived_refresh_info()
             followed += after["refreshes"] - before
-            if not root_changed:
+            if not root_changed:   # (a stroke that rewrites the root record is the one case left to a rebuild)
                 issued += n_updates
                 assert after["refreshes"] - before == n_updates, (stroke, cb)
             for cam in cams:
@@ -163,7 +148,7 @@ def test_descriptor_table_follows_brush_strokes_without_a_rebuild():
         assert issued >= 10 and followed >= issued, (followed, issued)   # none of those fell back to a rebuild
         # the same pool uploaded whole into a fresh table renders the same bytes (and has no garbage groups)
         grown = ctx.derived_info()["descriptors"]
-        ctx.pool_upload(o.getByteBuffer())
+        ctx.pool_upload(host)
         fresh = ctx.derived_info()["descriptors"]
         assert fresh <= grown
     finally:

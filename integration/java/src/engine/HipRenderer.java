@@ -344,7 +344,7 @@ public class HipRenderer {
 
   /**
    * svo_set_pick: the pixel readDepthPixel answers without waiting for its frame (default: the image centre, the crosshair of
-   * Main.java:139-141).  The frame's pick tile is drawn first and its lane writes the value to pinned host memory; a negative x
+   * Main.java:139-141).  A one-wave launch of its own, in front of the frame's kernels, writes the value to pinned host memory; a negative x
    * switches the pick off (every read-back then waits for the frame).
    */
   public void setPick(int x, int y) {

@@ -36,10 +36,19 @@ using namespace svo;
 
 static_assert(sizeof(svo_hit) == 16, "svo_hit must be 16 bytes");
 
+// The three output planes of a frame (or of a slot's frames): all allocated, or none (alloc_planes).
+struct Planes { uint32_t *color = nullptr; float *depth = nullptr; uint4 *hits = nullptr; };
+
+// One {stream, images} set of the library's own (svo_dispatch_async takes turns on them)
+struct ImageSet : Planes {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;   // behind the last overlapped dispatch into the set: a set is rendered into again only once that
+  bool used = false;           // frame is complete -- at most `overlap` frames are queued
+};
+
 struct svo_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;       // the stream dispatches go to: own_stream, or the caller's (svo_set_stream)
-  hipStream_t own_stream = nullptr;   // created with the context, kept for its lifetime
+  hipStream_t stream = nullptr;       // the stream dispatches go to: the current set's, or the caller's (svo_set_stream)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // pool
   uint8_t *d_pool = nullptr;
@@ -52,9 +61,6 @@ struct svo_ctx {
   int row_step = 1, out_y0 = 0, n_tile_rows = -1;  // stripe mode (svo_set_stripes); n_tile_rows < 0 = band mode
   int frame_number = 2, render_mode = 2, buffer_end = 0, use_beam = 0, bounces = 2, spp = 1, progressive = 0;
   int seq = 1, seq_fresh = 0;    // progressive: frames of the accumulation per dispatch, on a zeroed image or not (svo_set_sequence)
-  const FrameVar *batch_cams = nullptr;     // host copy of the cameras / frame numbers of the batch being submitted
-  FrameVar *batch_cams_dev = nullptr;       // (svo_ring_submit_cams), and where the slot keeps them on the device
-  void *batch_cams_slot = nullptr;          // the ring slot being submitted (its staging copy: ring_copy_cams)
   int batch = 1;                 // frames per dispatch (svo_set_batch)
   uint64_t frame_stride = 0;     // elements between consecutive frames of a batch in each output
   uint32_t mirror_mask = 0;
@@ -65,29 +71,21 @@ struct svo_ctx {
   float *d_depth = nullptr;
   uint4 *d_hits = nullptr;
   bool external_outputs = false;
-  uint32_t *own_color = nullptr;
-  float *own_depth = nullptr;
-  uint4 *own_hits = nullptr;
   // svo_dispatch_async takes turns on `overlap` sets {stream, images} while the library owns them (the reference's loop, Main.java:132-146,
-  // 257-289: frame N + 1 starts in frame N's tail): set 0 = own_stream + own_*, sets 1 .. overlap - 1 = alt_* (made on first use).
+  // 257-289: frame N + 1 starts in frame N's tail).  Set 0's stream is the context's own: made with it and kept for its lifetime, and
+  // its planes are the ones svo_resize makes.  The other sets' streams and planes, and every `done` event, are made on first use; the
+  // planes go with every svo_resize (free_outputs), the streams and events stay.
   // c->stream / c->d_* always name ONE set, the one of the last dispatch, so every read-back sees the last dispatched frame.
   static constexpr int kMaxSets = 8;
-  hipStream_t alt_stream[kMaxSets] = {};     // [0] unused: set 0 is own_stream / own_*
-  uint32_t *alt_color[kMaxSets] = {};
-  float *alt_depth[kMaxSets] = {};
-  uint4 *alt_hits[kMaxSets] = {};
-  hipEvent_t set_done[kMaxSets] = {};        // behind the last overlapped dispatch into each set (incl. set 0): a set is rendered
-  bool set_used[kMaxSets] = {};              // into again only once that frame is complete -- at most `overlap` frames are queued
+  ImageSet sets[kMaxSets];
   int cur_set = 0;
   int overlap = 4;             // image sets svo_dispatch_async takes turns on (svo_set_overlap; 1 = no alternation)
-  bool alt_inflight = false;   // a set that is not current may still have a frame in flight
-  hipStream_t set_stream(int k) const { return k == 0 ? own_stream : alt_stream[k]; }
+  bool others_inflight = false;   // a set that is not current may still have a frame in flight
   bool is_own_stream(hipStream_t st) const {
-    if (st == own_stream) return true;
-    for (int k = 1; k < kMaxSets; k++) if (alt_stream[k] && st == alt_stream[k]) return true;
+    for (const ImageSet &s : sets) if (s.stream && st == s.stream) return true;
     return false;
   }
-  // the pick pixel (svo_set_pick): answered from pinned host memory by the lane that stores it
+  // the pick pixel (svo_set_pick): answered from pinned host memory, written by a one-wave launch of its own (launch_pick)
   int pick_x = -1, pick_y = -1;
   bool pick_default = true;    // follows the image centre (the crosshair, Main.java:139-141) until svo_set_pick names a pixel
   uint32_t *pick_mail = nullptr;   // kPickSlots x kPickWords words of host memory the device writes
@@ -118,11 +116,10 @@ struct svo_ctx {
   PersistBuffers pb;
   // frames in flight behind the boundary (svo_ring_*): per slot a stream of its own, output buffers for up to
   // ring_frames consecutive frames, and the events around its last submission
-  struct RingSlot {
+  struct RingSlot : Planes {        // (the planes: library-owned images, frame after frame)
     hipStream_t stream = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipEvent_t e2 = nullptr;      // behind the forward copy of the last submission (svo_ring_forward_slot), made on demand
-    uint32_t *color = nullptr; float *depth = nullptr; uint4 *hits = nullptr;      // library-owned
     void *xcolor = nullptr, *xdepth = nullptr, *xhits = nullptr; uint64_t xstride = 0;   // caller-owned (svo_ring_bind_slot)
     int first_frame = 0, nframes = 0;
     bool used = false;
@@ -158,6 +155,62 @@ static int fail(svo_ctx *c, int code, const std::string &msg) {
 
 static constexpr uint64_t kPad = 64;  // zero bytes kept behind the pool (8-byte record loads may overhang)
 
+// Where one launch goes and which frames it renders.  make_frame, launch_beam, launch_frame, launch_frame_kernels and launch_pick
+// read these from here and everything else (render mode, bounces, spp, rows and stripes, pipeline, ...) from the context.
+struct Target {
+  hipStream_t stream = nullptr;
+  Planes out;
+  bool external = false;         // the planes are the caller's (svo_bind_outputs, svo_ring_bind_slot, a ring slot's frame range)
+  int batch = 1;                 // frames of the launch, frame_stride elements apart in each plane
+  uint64_t frame_stride = 0;
+  int frame_number = 0;
+  float cam[15] = {};
+  const FrameVar *cams = nullptr;         // per-frame cameras / frame numbers of the batch (svo_ring_submit_cams), on the host, ...
+  svo_ctx::RingSlot *cams_slot = nullptr; // ... and the slot that keeps them on the device (d_fvar) and stages the copy (ring_copy_cams)
+  enum Shape { kPlain, kRing, kOverlap } shape = kPlain;   // the persistent launch's shape unless svo_set_tuning named one
+  int overlap_sets = 0;                                    // kOverlap: the number of sets taking turns
+};
+
+// the context's own dispatch state: the set of the last dispatch (or the caller's stream and outputs), its camera and frame number
+static Target current_target(const svo_ctx *c) {
+  Target t;
+  t.stream = c->stream; t.out = {c->d_color, c->d_depth, c->d_hits}; t.external = c->external_outputs;
+  t.batch = c->batch; t.frame_stride = c->frame_stride; t.frame_number = c->frame_number;
+  memcpy(t.cam, c->cam, sizeof t.cam);
+  return t;
+}
+
+static void free_planes(Planes &p) {
+  if (p.color) (void)hipFree(p.color);
+  if (p.depth) (void)hipFree(p.depth);
+  if (p.hits) (void)hipFree(p.hits);
+  p = Planes();
+}
+
+// n_elems elements per plane, all planes or none: `out` is written only when every allocation succeeded
+static hipError_t alloc_planes(size_t n_elems, bool want_hits, Planes &out) {
+  Planes p;
+  hipError_t e = hipMalloc((void **)&p.color, n_elems * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&p.depth, n_elems * 4);
+  if (e == hipSuccess && want_hits) e = hipMalloc((void **)&p.hits, n_elems * 16);
+  if (e == hipSuccess) out = p;
+  else free_planes(p);
+  return e;
+}
+
+// every pool mutator starts here, before its argument checks: the pool is about to change (or to be handed out for writing), so
+// what was derived from it no longer describes it
+static void pool_changed(svo_ctx *c) {
+  if (c) { c->beam_live_valid = false; c->derived_valid = false; }
+}
+
+// waits for the frames in flight on every set's stream
+static int sync_own_streams(svo_ctx *c) {
+  for (ImageSet &s : c->sets) if (s.stream) HIPCHK(c, hipStreamSynchronize(s.stream));
+  c->others_inflight = false;
+  return SVO_OK;
+}
+
 extern "C" {
 
 int svo_create(int device, svo_ctx **out) {
@@ -172,17 +225,17 @@ int svo_create(int device, svo_ctx **out) {
   svo_ctx *c = new svo_ctx();
   c->device = device;
   c->stats.device = device;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->sets[0].stream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
       hipMalloc((void **)&c->d_counters, sizeof(DeviceCounters)) != hipSuccess) {
     delete c;
     return SVO_E_HIP;
   }
-  c->stream = c->own_stream;
+  c->stream = c->sets[0].stream;
   // the normal table: 65 536 x 16 bytes, a function of nothing but the code
   if (hipMalloc((void **)&c->d_ntab, 65536 * sizeof(float4)) == hipSuccess) {
-    hipLaunchKernelGGL(normal_table_kernel, dim3(256), dim3(256), 0, c->own_stream, c->d_ntab);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->own_stream) != hipSuccess) { (void)hipFree(c->d_ntab); c->d_ntab = nullptr; }
+    hipLaunchKernelGGL(normal_table_kernel, dim3(256), dim3(256), 0, c->sets[0].stream, c->d_ntab);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->sets[0].stream) != hipSuccess) { (void)hipFree(c->d_ntab); c->d_ntab = nullptr; }
   }
   c->pb.ntab = c->d_ntab;   // (null: the kernels decode in place)
   *out = c;
@@ -191,9 +244,7 @@ int svo_create(int device, svo_ctx **out) {
 
 static void ring_free(svo_ctx *c) {
   for (auto &s : c->ring) {
-    if (s.color) (void)hipFree(s.color);
-    if (s.depth) (void)hipFree(s.depth);
-    if (s.hits) (void)hipFree(s.hits);
+    free_planes(s);
     if (s.e0) (void)hipEventDestroy(s.e0);
     if (s.e1) (void)hipEventDestroy(s.e1);
     if (s.e2) (void)hipEventDestroy(s.e2);
@@ -210,19 +261,9 @@ static void ring_free(svo_ctx *c) {
 
 static void free_outputs(svo_ctx *c) {
   ring_free(c);   // the ring's images have the size of the frame
-  if (c->own_color) (void)hipFree(c->own_color);
-  if (c->own_depth) (void)hipFree(c->own_depth);
-  if (c->own_hits) (void)hipFree(c->own_hits);
-  c->own_color = nullptr; c->own_depth = nullptr; c->own_hits = nullptr;
-  for (int k = 1; k < svo_ctx::kMaxSets; k++) {
-    if (c->alt_color[k]) (void)hipFree(c->alt_color[k]);
-    if (c->alt_depth[k]) (void)hipFree(c->alt_depth[k]);
-    if (c->alt_hits[k]) (void)hipFree(c->alt_hits[k]);
-    c->alt_color[k] = nullptr; c->alt_depth[k] = nullptr; c->alt_hits[k] = nullptr;
-  }
-  if (c->cur_set != 0 && (c->is_own_stream(c->stream) || c->stream == nullptr)) c->stream = c->own_stream;
-  c->cur_set = 0; c->alt_inflight = false; c->pick_live = false;
-  for (int k = 0; k < svo_ctx::kMaxSets; k++) c->set_used[k] = false;
+  for (ImageSet &s : c->sets) { free_planes(s); s.used = false; }   // (the streams and the events stay)
+  if (c->cur_set != 0 && (c->is_own_stream(c->stream) || c->stream == nullptr)) c->stream = c->sets[0].stream;
+  c->cur_set = 0; c->others_inflight = false; c->pick_live = false;
   if (!c->external_outputs) { c->d_color = nullptr; c->d_depth = nullptr; c->d_hits = nullptr; }
 #if SVO_VARIANTS
   wavefront_free(c->wf);
@@ -252,11 +293,12 @@ int svo_destroy(svo_ctx *c) {
   ring_free(c);
   for (void *p : c->ipc_opened) if (p) (void)hipIpcCloseMemHandle(p);
   for (void *p : c->dev_allocs) if (p) (void)hipFree(p);
-  for (int k = 1; k < svo_ctx::kMaxSets; k++) if (c->alt_stream[k]) (void)hipStreamDestroy(c->alt_stream[k]);
-  for (int k = 0; k < svo_ctx::kMaxSets; k++) if (c->set_done[k]) (void)hipEventDestroy(c->set_done[k]);
   if (c->pick_stream) (void)hipStreamDestroy(c->pick_stream);
   if (c->pick_mail) (void)hipHostFree(c->pick_mail);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  for (ImageSet &s : c->sets) {
+    if (s.done) (void)hipEventDestroy(s.done);
+    if (s.stream) (void)hipStreamDestroy(s.stream);
+  }
   delete c;
   return SVO_OK;
 }
@@ -273,10 +315,10 @@ static int ensure_pool_capacity(svo_ctx *c, uint64_t need_len, bool keep) {
   uint64_t ncap = keep ? std::max<uint64_t>(need, c->pool_cap + c->pool_cap / 4) : need;
   uint8_t *np = nullptr;
   HIPCHK(c, hipMalloc((void **)&np, ncap));
-  HIPCHK(c, hipMemsetAsync(np, 0, ncap, c->own_stream));
+  HIPCHK(c, hipMemsetAsync(np, 0, ncap, c->sets[0].stream));
   if (keep && c->d_pool && c->pool_len)
-    HIPCHK(c, hipMemcpyAsync(np, c->d_pool, c->pool_len, hipMemcpyDeviceToDevice, c->own_stream));
-  HIPCHK(c, hipStreamSynchronize(c->own_stream));
+    HIPCHK(c, hipMemcpyAsync(np, c->d_pool, c->pool_len, hipMemcpyDeviceToDevice, c->sets[0].stream));
+  HIPCHK(c, hipStreamSynchronize(c->sets[0].stream));
   if (c->d_pool) HIPCHK(c, hipFree(c->d_pool));   // callers have synchronised the device: no frame still reads it
   c->d_pool = np;
   c->pool_cap = ncap;
@@ -291,20 +333,20 @@ static int refresh_dword0(svo_ctx *c) {
 }
 
 int svo_pool_reserve(svo_ctx *c, uint64_t nbytes) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
   int rc = ensure_pool_capacity(c, nbytes, false);
   if (rc) return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_pool, 0, c->pool_cap, c->own_stream));
-  HIPCHK(c, hipStreamSynchronize(c->own_stream));
+  HIPCHK(c, hipMemsetAsync(c->d_pool, 0, c->pool_cap, c->sets[0].stream));
+  HIPCHK(c, hipStreamSynchronize(c->sets[0].stream));
   c->pool_len = nbytes;
   return SVO_OK;
 }
 
 int svo_pool_upload_device(svo_ctx *c, const void *dptr, uint64_t nbytes) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c || (!dptr && nbytes)) return fail(c, SVO_E_INVALID, "svo_pool_upload_device: null buffer");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
@@ -317,7 +359,7 @@ int svo_pool_upload_device(svo_ctx *c, const void *dptr, uint64_t nbytes) {
 }
 
 int svo_pool_upload(svo_ctx *c, const void *host, uint64_t nbytes) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c || (!host && nbytes)) return fail(c, SVO_E_INVALID, "svo_pool_upload: null buffer");
   HIPCHK(c, hipSetDevice(c->device));
   // frames may be in flight on any stream the caller has handed over (svo_set_stream): the pool changes only
@@ -341,7 +383,7 @@ int svo_pool_update(svo_ctx *c, const void *host_base, uint64_t start, uint64_t 
   const bool follow = true;
 #endif
   const bool had_table = c && follow && c->derived_valid && c->dt.ok;
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c || !host_base) return fail(c, SVO_E_INVALID, "svo_pool_update: null buffer");
   if (start >= end) return fail(c, SVO_E_INVALID, "Update SSBO error: Invalid parameters.");
   if (!c->d_pool) return fail(c, SVO_E_NOPOOL, "svo_pool_update before svo_pool_upload");
@@ -356,7 +398,7 @@ int svo_pool_update(svo_ctx *c, const void *host_base, uint64_t start, uint64_t 
   if (start < 4) { int rc = refresh_dword0(c); if (rc) return rc; }
   if (had_table) {
     bool refreshed = false;
-    hipError_t e = derive::refresh_table(c->dt, c->d_pool, c->pool_len, start, end, c->own_stream, &refreshed);
+    hipError_t e = derive::refresh_table(c->dt, c->d_pool, c->pool_len, start, end, c->sets[0].stream, &refreshed);
     if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("descriptor table refresh: ") + hipGetErrorString(e));
     c->derived_valid = refreshed;   // false: the next dispatch builds it anew
   }
@@ -374,7 +416,7 @@ int svo_pool_download(svo_ctx *c, void *host, uint64_t nbytes) {
 }
 
 int svo_pool_device_ptr(svo_ctx *c, void **dptr, uint64_t *nbytes) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c || !dptr) return SVO_E_INVALID;
   *dptr = c->d_pool;
   if (nbytes) *nbytes = c->pool_len;
@@ -387,7 +429,7 @@ int svo_pool_device_ptr(svo_ctx *c, void **dptr, uint64_t *nbytes) {
 }
 
 int svo_pool_commit(svo_ctx *c) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }
+  pool_changed(c);
   if (!c) return SVO_E_INVALID;
   if (!c->d_pool) return fail(c, SVO_E_NOPOOL, "svo_pool_commit: no pool");
   HIPCHK(c, hipSetDevice(c->device));
@@ -403,8 +445,18 @@ __global__ void count_zero_bytes_kernel(const uint8_t *p, size_t n, unsigned int
   if (z) atomicAdd(zeros, z);
 }
 
+// the tail of both builders: `e` is what the build returned; a pool that fits replaces the context's
+static int adopt_built_pool(svo_ctx *c, hipError_t e, const build::Result &r, bool too_large, uint64_t *out_nbytes, const char *who) {
+  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (out_nbytes) *out_nbytes = r.len;
+  if (too_large) return fail(c, SVO_E_TOOLARGE, "pool must stay below 2^31 bytes");
+  if (c->d_pool) (void)hipFree(c->d_pool);
+  c->d_pool = r.pool; c->pool_len = r.len; c->pool_cap = r.cap;
+  return refresh_dword0(c);
+}
+
 int svo_build_from_heightmap(svo_ctx *c, const uint16_t *height, const uint8_t *material, int n, uint64_t *out_nbytes) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c || !height || !material) return fail(c, SVO_E_INVALID, "svo_build_from_heightmap: null map");
   if (n < 8 || n > 8192 || (n & (n - 1))) return fail(c, SVO_E_INVALID, "svo_build_from_heightmap: n must be a power of two in 8..8192");
   HIPCHK(c, hipSetDevice(c->device));
@@ -417,30 +469,22 @@ int svo_build_from_heightmap(svo_ctx *c, const uint16_t *height, const uint8_t *
   hipError_t e = hipMalloc((void **)&d_h, cells * 2);
   if (e == hipSuccess) e = hipMalloc((void **)&d_m, cells);
   if (e == hipSuccess) e = hipMalloc((void **)&d_z, 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_h, height, cells * 2, hipMemcpyHostToDevice, c->own_stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_m, material, cells, hipMemcpyHostToDevice, c->own_stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_z, 0, 4, c->own_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_h, height, cells * 2, hipMemcpyHostToDevice, c->sets[0].stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_m, material, cells, hipMemcpyHostToDevice, c->sets[0].stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_z, 0, 4, c->sets[0].stream);
   unsigned int zeros = 0;
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(count_zero_bytes_kernel, dim3(1024), dim3(256), 0, c->own_stream, d_m, cells, d_z);
-    e = hipMemcpyAsync(&zeros, d_z, 4, hipMemcpyDeviceToHost, c->own_stream);
+    hipLaunchKernelGGL(count_zero_bytes_kernel, dim3(1024), dim3(256), 0, c->sets[0].stream, d_m, cells, d_z);
+    e = hipMemcpyAsync(&zeros, d_z, 4, hipMemcpyDeviceToHost, c->sets[0].stream);
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->own_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->sets[0].stream);
   if (e != hipSuccess) { cleanup(); return fail(c, SVO_E_HIP, std::string("svo_build_from_heightmap: ") + hipGetErrorString(e)); }
   if (zeros) { cleanup(); return fail(c, SVO_E_INVALID, "svo_build_from_heightmap: material 0 in the material map (0 is the empty voxel)"); }
   build::Result r;
   bool too_large = false;
-  e = build::build_pool(d_h, d_m, n, kPad, c->own_stream, r, &too_large);
+  e = build::build_pool(d_h, d_m, n, kPad, c->sets[0].stream, r, &too_large);
   cleanup();
-  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("svo_build_from_heightmap: ") + hipGetErrorString(e));
-  if (too_large) {
-    if (out_nbytes) *out_nbytes = r.len;
-    return fail(c, SVO_E_TOOLARGE, "pool must stay below 2^31 bytes");
-  }
-  if (c->d_pool) (void)hipFree(c->d_pool);
-  c->d_pool = r.pool; c->pool_len = r.len; c->pool_cap = r.cap;
-  if (out_nbytes) *out_nbytes = r.len;
-  return refresh_dword0(c);
+  return adopt_built_pool(c, e, r, too_large, out_nbytes, "svo_build_from_heightmap");
 }
 
 int svo_build_from_heightmap16(svo_ctx *c, const uint16_t *raw16, const uint8_t *material, int n, uint64_t *out_nbytes) {
@@ -453,7 +497,7 @@ int svo_build_from_heightmap16(svo_ctx *c, const uint16_t *raw16, const uint8_t 
 }
 
 int svo_build_from_voxels(svo_ctx *c, const uint8_t *voxels, int n, uint64_t *out_nbytes) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }   // the pool is about to change (or to be handed out for writing)
+  pool_changed(c);
   if (!c || !voxels) return fail(c, SVO_E_INVALID, "svo_build_from_voxels: null grid");
   if (n < 2 || n > 1024 || (n & (n - 1))) return fail(c, SVO_E_INVALID, "svo_build_from_voxels: n must be a power of two in 2..1024");
   HIPCHK(c, hipSetDevice(c->device));
@@ -461,20 +505,12 @@ int svo_build_from_voxels(svo_ctx *c, const uint8_t *voxels, int n, uint64_t *ou
   const size_t cells = (size_t)n * (size_t)n * (size_t)n;
   uint8_t *d_v = nullptr;
   hipError_t e = hipMalloc((void **)&d_v, cells);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_v, voxels, cells, hipMemcpyHostToDevice, c->own_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_v, voxels, cells, hipMemcpyHostToDevice, c->sets[0].stream);
   build::Result r;
   bool too_large = false;
-  if (e == hipSuccess) e = build::build_pool_from_voxels(d_v, n, kPad, c->own_stream, r, &too_large);
+  if (e == hipSuccess) e = build::build_pool_from_voxels(d_v, n, kPad, c->sets[0].stream, r, &too_large);
   if (d_v) (void)hipFree(d_v);
-  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("svo_build_from_voxels: ") + hipGetErrorString(e));
-  if (too_large) {
-    if (out_nbytes) *out_nbytes = r.len;
-    return fail(c, SVO_E_TOOLARGE, "pool must stay below 2^31 bytes");
-  }
-  if (c->d_pool) (void)hipFree(c->d_pool);
-  c->d_pool = r.pool; c->pool_len = r.len; c->pool_cap = r.cap;
-  if (out_nbytes) *out_nbytes = r.len;
-  return refresh_dword0(c);
+  return adopt_built_pool(c, e, r, too_large, out_nbytes, "svo_build_from_voxels");
 }
 
 // ---------------------------------------------------------------- frame state
@@ -498,20 +534,19 @@ int svo_set_params(svo_ctx *c, int frame_number, int render_mode, int buffer_end
 int svo_resize(svo_ctx *c, int width, int height) {
   if (!c || width <= 0 || height <= 0) return fail(c, SVO_E_INVALID, "svo_resize: bad size");
   HIPCHK(c, hipSetDevice(c->device));
-  if (width == c->width && height == c->height && c->own_color) return SVO_OK;
+  ImageSet &own = c->sets[0];
+  if (width == c->width && height == c->height && own.color) return SVO_OK;
   HIPCHK(c, hipDeviceSynchronize());   // frames in flight on other streams still write the old images
   free_outputs(c);
   const size_t n = (size_t)width * (size_t)height;
-  HIPCHK(c, hipMalloc((void **)&c->own_color, n * 4));
-  HIPCHK(c, hipMalloc((void **)&c->own_depth, n * 4));
-  HIPCHK(c, hipMalloc((void **)&c->own_hits, n * 16));
-  HIPCHK(c, hipMemset(c->own_color, 0, n * 4));
-  HIPCHK(c, hipMemset(c->own_depth, 0, n * 4));
-  HIPCHK(c, hipMemset(c->own_hits, 0, n * 16));
+  HIPCHK(c, alloc_planes(n, true, own));
+  HIPCHK(c, hipMemset(own.color, 0, n * 4));
+  HIPCHK(c, hipMemset(own.depth, 0, n * 4));
+  HIPCHK(c, hipMemset(own.hits, 0, n * 16));
   // hipMemset is asynchronous and the dispatch streams do not synchronise with the null stream: without this wait the
   // zeroing can land after the first frame's stores (seen as all-zero hit records of sky pixels)
   HIPCHK(c, hipDeviceSynchronize());
-  if (!c->external_outputs) { c->d_color = c->own_color; c->d_depth = c->own_depth; c->d_hits = c->own_hits; }
+  if (!c->external_outputs) { c->d_color = own.color; c->d_depth = own.depth; c->d_hits = own.hits; }
   c->width = width; c->height = height;
   if (c->pick_default) { c->pick_x = width / 2; c->pick_y = height / 2; }   // the crosshair: Main.java:139-141 reads (WIDTH / 2, HEIGHT / 2)
   else if (c->pick_x >= width || c->pick_y >= height) { c->pick_x = -1; c->pick_y = -1; }
@@ -525,8 +560,8 @@ int svo_bind_outputs(svo_ctx *c, void *color, void *depth, void *hits) {
   c->pick_live = false;
   if (!color) {
     c->external_outputs = false;
-    const int k = (c->cur_set != 0 && c->alt_color[c->cur_set]) ? c->cur_set : 0;
-    c->d_color = k ? c->alt_color[k] : c->own_color; c->d_depth = k ? c->alt_depth[k] : c->own_depth; c->d_hits = k ? c->alt_hits[k] : c->own_hits;
+    const ImageSet &s = c->sets[c->cur_set];   // (a set is current only once it has its planes)
+    c->d_color = s.color; c->d_depth = s.depth; c->d_hits = s.hits;
     return SVO_OK;
   }
   if (!depth) return fail(c, SVO_E_INVALID, "svo_bind_outputs: depth buffer required");
@@ -658,20 +693,19 @@ int svo_set_hit_records(svo_ctx *c, int enabled) {
 int svo_set_stream(svo_ctx *c, void *hip_stream) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  // no synchronisation here: a caller may alternate streams to keep two frames in flight
-  // (different output buffers); ordering between streams is the caller's business.  The library's own stream lives as
-  // long as the context: NULL returns to it.
+  // Between two streams of the caller's there is no synchronisation here: a caller may alternate streams to keep two frames in
+  // flight (different output buffers); ordering between them is the caller's business.  Leaving the library's own streams waits for
+  // them (below).  They live as long as the context: NULL returns to the current set's.
   if (hip_stream) {
     // leaving the library's own streams: what they still have in flight writes the library's images, which dispatches on the
     // caller's stream may render into next
-    if (c->alt_inflight || c->is_own_stream(c->stream)) {
-      HIPCHK(c, hipStreamSynchronize(c->own_stream));
-      for (int k = 1; k < svo_ctx::kMaxSets; k++) if (c->alt_stream[k]) HIPCHK(c, hipStreamSynchronize(c->alt_stream[k]));
-      c->alt_inflight = false;
+    if (c->others_inflight || c->is_own_stream(c->stream)) {
+      int rc = sync_own_streams(c);
+      if (rc) return rc;
     }
     c->stream = (hipStream_t)hip_stream;
   } else {
-    c->stream = (c->cur_set != 0 && c->alt_stream[c->cur_set]) ? c->alt_stream[c->cur_set] : c->own_stream;   // the current set's own
+    c->stream = c->sets[c->cur_set].stream;
   }
   c->pick_live = false;
   return SVO_OK;
@@ -679,7 +713,7 @@ int svo_set_stream(svo_ctx *c, void *hip_stream) {
 
 int svo_set_overlap(svo_ctx *c, int sets) {
   if (!c) return SVO_E_INVALID;
-  // 0: one set (no alternation); 1: the default number of sets; 2 .. 4: that many
+  // 0: one set (no alternation); 1: the default number of sets; 2 .. kMaxSets (8): that many
   if (sets < 0 || sets > svo_ctx::kMaxSets) return fail(c, SVO_E_INVALID, "svo_set_overlap: 0 (off), 1 (the default number of sets) or 2 .. 8 sets");
   c->overlap = sets == 0 ? 1 : (sets == 1 ? 4 : sets);
   return SVO_OK;
@@ -703,39 +737,45 @@ int svo_set_pick(svo_ctx *c, int x, int y) {
 }
 
 // ---------------------------------------------------------------- dispatch
-static int make_frame(svo_ctx *c, Frame &f) {
+// The output row just past the last one a frame writes; f.out_y0 when it writes none (its stripes all start below the image).
+// Tile row j covers image rows y0 + 8 j row_step ..., clipped to min(height, y1), and lands at output rows out_y0 + 8 j ...
+static int last_written_row(const Frame &f) {
+  const long long yend = std::min(f.height, f.y1);
+  for (int j = f.tiles_y - 1; j >= 0; j--) {
+    const long long gy = (long long)f.y0 + (long long)j * 8 * f.row_step;
+    if (gy < yend) return f.out_y0 + j * 8 + (int)std::min<long long>(8, yend - gy);
+  }
+  return f.out_y0;
+}
+
+static int make_frame(svo_ctx *c, const Target &t, Frame &f) {
   if (!c->d_pool || c->pool_len < 7) return fail(c, SVO_E_NOPOOL, "svo_dispatch: no pool uploaded");
-  if (!c->d_color) return fail(c, SVO_E_INVALID, "svo_dispatch: svo_resize not called");
-  memcpy(f.cam, c->cam, sizeof f.cam);
+  if (!t.out.color) return fail(c, SVO_E_INVALID, "svo_dispatch: svo_resize not called");
+  memcpy(f.cam, t.cam, sizeof f.cam);
   f.width = c->width; f.height = c->height;
   f.y0 = std::min(c->y0, c->height);
   f.y1 = std::min(c->y1, c->height);
   f.row_step = c->row_step;
   f.out_y0 = c->n_tile_rows < 0 ? f.y0 : c->out_y0;
-  f.frame_number = c->frame_number; f.render_mode = c->render_mode;
+  f.frame_number = t.frame_number; f.render_mode = c->render_mode;
   f.bounces = c->bounces; f.spp = c->spp; f.mirror_mask = c->mirror_mask;
   f.pool_len = (uint32_t)c->pool_len;
   f.dword0 = c->dword0;
   f.tiles_x = (c->width + 7) / 8;
   f.tiles_y = c->n_tile_rows < 0 ? (f.y1 - f.y0 + 7) / 8 : c->n_tile_rows;
   f.ntiles = f.tiles_x * f.tiles_y;
-  f.write_hits = (c->write_hits && c->d_hits) ? 1 : 0;
+  f.write_hits = (c->write_hits && t.out.hits) ? 1 : 0;
   f.use_beam = 0; f.beam_w = 0; f.beam = nullptr;
   f.progressive = c->progressive;
   f.batch = 1; f.frame_stride = 0; f.seq = 1;
-  if (!c->external_outputs && c->n_tile_rows > 0) {
+  if (!t.external && c->n_tile_rows > 0) {
     // packed stripes land at output rows out_y0 + 8 j + ly: they must stay inside the library's W x H images
-    // (caller-owned gather buffers are the caller's to size, see svo_bind_outputs)
-    int last = -1;
-    for (int j = c->n_tile_rows - 1; j >= 0; j--)
-      if ((long long)f.y0 + (long long)j * 8 * f.row_step < (long long)f.height) { last = j; break; }
-    if (last >= 0) {
-      const int gy = f.y0 + last * 8 * f.row_step;
-      const int rows = std::min(8, f.height - gy);
-      if (f.out_y0 + last * 8 + rows > f.height)
-        return fail(c, SVO_E_INVALID, "svo_set_stripes: packed stripes do not fit the library-owned images; bind "
-                                      "caller-owned outputs that cover out_row0 + 8 * n_tile_rows rows");
-    }
+    // (caller-owned gather buffers are the caller's to size, see svo_bind_outputs).  Stripes that write no row fit anywhere.
+    // (stripe mode: y1 is the image's height, tiles_y is n_tile_rows)
+    const int end = last_written_row(f);
+    if (end > f.out_y0 && end > f.height)
+      return fail(c, SVO_E_INVALID, "svo_set_stripes: packed stripes do not fit the library-owned images; bind "
+                                    "caller-owned outputs that cover out_row0 + 8 * n_tile_rows rows");
   }
   return SVO_OK;
 }
@@ -746,7 +786,7 @@ static size_t out_elems(const svo_ctx *c, const Frame &f) {
 }
 
 // the coarse pass of useBeamOptimization (Main.java:257-266), enqueued in front of the frame's trace kernels
-static int launch_beam(svo_ctx *c, Frame &f, int &set) {
+static int launch_beam(svo_ctx *c, const Target &t, Frame &f, int &set) {
   const int bw = (f.width + kBeamBlock - 1) / kBeamBlock, bh = (f.height + kBeamBlock - 1) / kBeamBlock;
   const size_t need = (size_t)bw * (size_t)bh;
   if (c->beam_cap < need) {
@@ -767,25 +807,25 @@ static int launch_beam(svo_ctx *c, Frame &f, int &set) {
     if (!c->d_beam_live) HIPCHK(c, hipMalloc((void **)&c->d_beam_live, kBeamLiveBytes));
     for (int d = kBeamTop; d >= 1; d--) {
       const unsigned n = 1u << (3 * d);
-      hipLaunchKernelGGL(beam_live_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_pool, (uint32_t)c->pool_len, d,
+      hipLaunchKernelGGL(beam_live_kernel, dim3((n + 255) / 256), dim3(256), 0, t.stream, c->d_pool, (uint32_t)c->pool_len, d,
                          c->d_beam_live);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(t.stream));
     c->beam_live_valid = true;
   }
   set = (int)(c->beam_frames++ % svo_ctx::kBeamSets);
-  if (c->beam_used[set]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->beam_done[set], 0));
+  if (c->beam_used[set]) HIPCHK(c, hipStreamWaitEvent(t.stream, c->beam_done[set], 0));
   BeamArgs a;
   a.pool = c->d_pool; a.live = c->d_beam_live; a.f = f; a.beam = c->d_beam[set]; a.beam_w = bw; a.beam_h = bh;
   a.cam_ok = beam_camera_ok(f.cam);
-  hipLaunchKernelGGL(beam_kernel, dim3((unsigned)((bw + 7) / 8), (unsigned)(f.tiles_y * 2)), dim3(64), 0, c->stream, a);
+  hipLaunchKernelGGL(beam_kernel, dim3((unsigned)((bw + 7) / 8), (unsigned)(f.tiles_y * 2)), dim3(64), 0, t.stream, a);
   HIPCHK(c, hipGetLastError());
   f.use_beam = 1; f.beam_w = bw; f.beam = c->d_beam[set];
   return SVO_OK;
 }
 
-static int launch_frame_kernels(svo_ctx *c, Frame &f, bool count, uint32_t *color, float *depth, uint4 *hits);
+static int launch_frame_kernels(svo_ctx *c, const Target &t, Frame &f, bool count, uint32_t *color, float *depth, uint4 *hits);
 
 // The descriptor table follows the pool: (re)built at the first dispatch after a pool change.  Every pool mutator has
 // synchronised the device, except a caller writing through svo_pool_device_ptr -- so wait for the device here too: no
@@ -793,90 +833,80 @@ static int launch_frame_kernels(svo_ctx *c, Frame &f, bool count, uint32_t *colo
 static int ensure_derived(svo_ctx *c) {
   if (c->derived_valid) return SVO_OK;
   HIPCHK(c, hipDeviceSynchronize());
-  hipError_t e = derive::build_table(c->dt, c->d_pool, c->pool_len, c->own_stream);
+  hipError_t e = derive::build_table(c->dt, c->d_pool, c->pool_len, c->sets[0].stream);
   if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("descriptor table: ") + hipGetErrorString(e));
   c->derived_valid = true;
   return SVO_OK;
 }
 
-static int launch_frame(svo_ctx *c, bool count) {
+static int launch_frame(svo_ctx *c, const Target &t, bool count) {
   Frame f;
-  int rc = make_frame(c, f);
+  int rc = make_frame(c, t, f);
   if (rc) return rc;
   if (f.ntiles <= 0) return SVO_OK;
   int beam_set = -1;
   if (c->use_beam) {
-    rc = launch_beam(c, f, beam_set);
+    rc = launch_beam(c, t, f, beam_set);
     if (rc) return rc;
   }
-  const int nb = count ? 1 : c->batch;
-  if (nb > 1 && !c->external_outputs)
+  const int nb = count ? 1 : t.batch;
+  if (nb > 1 && !t.external)
     return fail(c, SVO_E_INVALID, "svo_set_batch: a batch renders into caller-owned outputs (svo_bind_outputs)");
-  if (nb > 1) {
-    // frame k lands frame_stride elements behind frame k - 1: the stride must cover the rows one frame writes, or the
-    // frames of the batch overwrite one another
-    int last_row = 0;
-    for (int j = f.tiles_y - 1; j >= 0; j--) {
-      const long long gy = (long long)f.y0 + (long long)j * 8 * f.row_step;
-      if (gy < (long long)std::min(f.height, f.y1)) { last_row = f.out_y0 + j * 8 + (int)std::min<long long>(8, std::min(f.height, f.y1) - gy); break; }
-    }
-    if (c->frame_stride < (uint64_t)last_row * (uint64_t)f.width)
-      return fail(c, SVO_E_INVALID, "svo_set_batch: frame_stride is smaller than the rows one frame writes");
-  }
+  const int last_row = last_written_row(f);
+  const bool writes_rows = last_row > f.out_y0;
+  // frame k lands frame_stride elements behind frame k - 1: the stride must cover the rows one frame writes, or the
+  // frames of the batch overwrite one another
+  if (nb > 1 && writes_rows && t.frame_stride < (uint64_t)last_row * (uint64_t)f.width)
+    return fail(c, SVO_E_INVALID, "svo_set_batch: frame_stride is smaller than the rows one frame writes");
   if (nb > 1 && f.progressive)
     return fail(c, SVO_E_INVALID, "svo_set_batch: cross-frame accumulation blends into ONE image frame after frame; "
                                   "a batch writes every frame to its own");
-  if (nb > 1 && c->batch_cams && c->use_beam)
+  if (nb > 1 && t.cams && c->use_beam)
     return fail(c, SVO_E_INVALID, "svo_ring_submit_cams: the beam pre-pass belongs to one camera; submit such frames one by one");
+  const Planes &o = t.out;
   if (f.progressive && (c->seq > 1 || c->seq_fresh) && !count) {
     // a progressive sequence: c->seq frames of the accumulation, frameNumber, frameNumber + 1, ..., into the one image
-    if (c->seq_fresh) {   // ... starting on a zeroed image (the application's first frames; the image after glTexStorage2D)
-      int last_row = f.out_y0;
-      for (int j = f.tiles_y - 1; j >= 0; j--) {
-        const long long gy = (long long)f.y0 + (long long)j * 8 * f.row_step;
-        if (gy < (long long)std::min(f.height, f.y1)) { last_row = f.out_y0 + j * 8 + (int)std::min<long long>(8, std::min(f.height, f.y1) - gy); break; }
-      }
-      if (last_row > f.out_y0)
-        HIPCHK(c, hipMemsetAsync(c->d_color + (size_t)f.out_y0 * (size_t)f.width, 0, (size_t)(last_row - f.out_y0) * (size_t)f.width * 4, c->stream));
-    }
+    // ... starting on a zeroed image when asked (the application's first frames; the image after glTexStorage2D)
+    if (c->seq_fresh && writes_rows)
+      HIPCHK(c, hipMemsetAsync(o.color + (size_t)f.out_y0 * (size_t)f.width, 0, (size_t)(last_row - f.out_y0) * (size_t)f.width * 4, t.stream));
     Frame probe = f;
     if (c->pipeline == 1 && f.spp <= 1 && persist_can_fold(probe, c->seq)) {
       // the persistent pipeline carries the whole sequence in one launch and blends it in frame order afterwards
       f.seq = c->seq;
-      rc = launch_frame_kernels(c, f, count, c->d_color, c->d_depth, c->d_hits);
+      rc = launch_frame_kernels(c, t, f, count, o.color, o.depth, o.hits);
     } else {
       for (int k = 0; k < c->seq && rc == SVO_OK; k++) {
         Frame g = f;
         g.frame_number = f.frame_number + k;
-        rc = launch_frame_kernels(c, g, count, c->d_color, c->d_depth, c->d_hits);
+        rc = launch_frame_kernels(c, t, g, count, o.color, o.depth, o.hits);
       }
     }
   } else if (nb > 1 && c->pipeline == 1) {
     // the persistent pipeline takes the whole batch as one launch: its waves go from frame to frame without a tail
     f.batch = nb;
-    f.frame_stride = (uint32_t)c->frame_stride;
-    rc = launch_frame_kernels(c, f, count, c->d_color, c->d_depth, c->d_hits);
+    f.frame_stride = (uint32_t)t.frame_stride;
+    rc = launch_frame_kernels(c, t, f, count, o.color, o.depth, o.hits);
   } else {
     for (int k = 0; k < nb && rc == SVO_OK; k++) {
       Frame g = f;
       g.frame_number = f.frame_number + k;
-      if (c->batch_cams) { memcpy(g.cam, c->batch_cams[k].cam, sizeof g.cam); g.frame_number = c->batch_cams[k].frame_number; }
-      const size_t o = (size_t)k * (size_t)c->frame_stride;
-      rc = launch_frame_kernels(c, g, count, c->d_color + o, c->d_depth + o, c->d_hits ? c->d_hits + o : nullptr);
+      if (t.cams) { memcpy(g.cam, t.cams[k].cam, sizeof g.cam); g.frame_number = t.cams[k].frame_number; }
+      const size_t at = (size_t)k * (size_t)t.frame_stride;
+      rc = launch_frame_kernels(c, t, g, count, o.color + at, o.depth + at, o.hits ? o.hits + at : nullptr);
     }
   }
   if (rc == SVO_OK && beam_set >= 0) {
-    HIPCHK(c, hipEventRecord(c->beam_done[beam_set], c->stream));
+    HIPCHK(c, hipEventRecord(c->beam_done[beam_set], t.stream));
     c->beam_used[beam_set] = true;
   }
   return rc;
 }
 
-static int ring_copy_cams(void *ctx);
+static int ring_copy_cams(void *target);
 
-static int launch_frame_kernels(svo_ctx *c, Frame &f, bool count, uint32_t *color, float *depth, uint4 *hits) {
+static int launch_frame_kernels(svo_ctx *c, const Target &t, Frame &f, bool count, uint32_t *color, float *depth, uint4 *hits) {
   int rc = SVO_OK;
-  if (count) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(DeviceCounters), c->stream));
+  if (count) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(DeviceCounters), t.stream));
   if (c->pipeline == 1 && !count) {
 #if SVO_VARIANTS
     static const int env_mode = getenv("SVO_DERIVED") ? atoi(getenv("SVO_DERIVED")) : -1;   // A/B override
@@ -886,15 +916,19 @@ static int launch_frame_kernels(svo_ctx *c, Frame &f, bool count, uint32_t *colo
     const int mode = env_mode >= 0 ? env_mode : c->derived_mode;
     if (mode != 0 && (rc = ensure_derived(c)) != SVO_OK) return rc;
     const bool walk_table = mode != 0 && c->dt.ok;   // not derivable (deeper than 13 levels, cyclic): the records are walked
-    rc = persist_launch(c->pb, c->d_pool, f, color, depth, hits, out_elems(c, f), c->stream, walk_table ? c->dt.desc : nullptr,
-                        walk_table ? c->dt.aux : nullptr, walk_table ? c->dt.count : 0u, c->batch_cams ? c->batch_cams_dev : nullptr,
-                        c->batch_cams, ring_copy_cams, c);
+    // the target's launch-shape hint reaches persist_launch through these three, set for the one call
+    c->pb.in_ring = t.shape == Target::kRing; c->pb.in_overlap = t.shape == Target::kOverlap;
+    if (c->pb.in_overlap) c->pb.overlap_sets = t.overlap_sets;
+    rc = persist_launch(c->pb, c->d_pool, f, color, depth, hits, out_elems(c, f), t.stream, walk_table ? c->dt.desc : nullptr,
+                        walk_table ? c->dt.aux : nullptr, walk_table ? c->dt.count : 0u, t.cams ? t.cams_slot->d_fvar : nullptr,
+                        t.cams, ring_copy_cams, (void *)&t);
+    c->pb.in_ring = false; c->pb.in_overlap = false;
     if (rc) return fail(c, SVO_E_HIP, std::string("persistent pipeline: ") + hipGetErrorString((hipError_t)rc));
     return SVO_OK;
   }
 #if SVO_VARIANTS
   if (c->pipeline == 2 && !count) {
-    rc = wavefront_launch(c->wf, c->d_pool, f, color, depth, hits, out_elems(c, f), c->stream);
+    rc = wavefront_launch(c->wf, c->d_pool, f, color, depth, hits, out_elems(c, f), t.stream);
     if (rc) return fail(c, SVO_E_HIP, std::string("wavefront pipeline: ") + hipGetErrorString((hipError_t)rc));
     return SVO_OK;
   }
@@ -902,9 +936,9 @@ static int launch_frame_kernels(svo_ctx *c, Frame &f, bool count, uint32_t *colo
   const int per = (f.ntiles + 7) / 8;
   dim3 grid((unsigned)(per * 8)), block(64);
   if (count)
-    hipLaunchKernelGGL(trace_fused_kernel<true>, grid, block, 0, c->stream, c->d_pool, f, color, depth, hits, c->d_counters);
+    hipLaunchKernelGGL(trace_fused_kernel<true>, grid, block, 0, t.stream, c->d_pool, f, color, depth, hits, c->d_counters);
   else
-    hipLaunchKernelGGL(trace_fused_kernel<false>, grid, block, 0, c->stream, c->d_pool, f, color, depth, hits, c->d_counters);
+    hipLaunchKernelGGL(trace_fused_kernel<false>, grid, block, 0, t.stream, c->d_pool, f, color, depth, hits, c->d_counters);
   HIPCHK(c, hipGetLastError());
   return SVO_OK;
 }
@@ -913,11 +947,11 @@ static int launch_frame_kernels(svo_ctx *c, Frame &f, bool count, uint32_t *colo
 // frame's kernels; a mail slot of its own per dispatch (kPickSlots of them, round-robin).  Frames the live shader's store
 // applies to: one sample per pixel, no cross-frame accumulation, no batch, no beam pre-pass (its start distances change the
 // iteration count of the hit record), the whole frame (a rank's stripes / a row band may not even contain the pixel).
-static int launch_pick(svo_ctx *c) {
+static int launch_pick(svo_ctx *c, const Target &t) {
   c->pick_live = false;
-  if (c->pick_x < 0 || c->batch != 1 || c->progressive || c->spp != 1 || c->use_beam || c->rows_set || c->n_tile_rows >= 0) return SVO_OK;
+  if (c->pick_x < 0 || t.batch != 1 || c->progressive || c->spp != 1 || c->use_beam || c->rows_set || c->n_tile_rows >= 0) return SVO_OK;
   Frame f;
-  int rc = make_frame(c, f);
+  int rc = make_frame(c, t, f);
   if (rc) return rc;
   if (f.ntiles <= 0 || c->pick_x >= f.width || c->pick_y >= f.height) return SVO_OK;
   // (the pick is a convenience: a runtime that cannot give it its mail or its stream leaves every read-back on the waiting path)
@@ -951,44 +985,42 @@ static int launch_pick(svo_ctx *c) {
 int svo_dispatch_async(svo_ctx *c) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  // Two sets {stream, images} in turn while the library owns both and nothing ties a frame to the image before it: the next
-  // frame's persistent waves take the CUs this frame's tail frees (glDispatchCompute only enqueues as well: Renderer.java:118-121).
-  const bool own = !c->external_outputs && c->own_color && c->is_own_stream(c->stream);
-  if (c->overlap > 1 && own && c->pipeline == 1 && !c->progressive && c->batch == 1) {
+  // Up to kMaxSets (8) sets {stream, images} in turn while the library owns them and nothing ties a frame to the image before it: the
+  // next frame's persistent waves take the CUs this frame's tail frees (glDispatchCompute only enqueues as well: Renderer.java:118-121).
+  const bool own = !c->external_outputs && c->sets[0].color && c->is_own_stream(c->stream);
+  const bool overlapped = c->overlap > 1 && own && c->pipeline == 1 && !c->progressive && c->batch == 1;
+  if (overlapped) {
     const int k = (c->cur_set + 1) % c->overlap;
-    if (k != 0) {
-      if (!c->alt_stream[k]) HIPCHK(c, hipStreamCreateWithFlags(&c->alt_stream[k], hipStreamNonBlocking));
-      if (!c->alt_color[k]) {
-        const size_t n = (size_t)c->width * (size_t)c->height;
-        HIPCHK(c, hipMalloc((void **)&c->alt_color[k], n * 4));
-        HIPCHK(c, hipMalloc((void **)&c->alt_depth[k], n * 4));
-        HIPCHK(c, hipMalloc((void **)&c->alt_hits[k], n * 16));
-        HIPCHK(c, hipMemsetAsync(c->alt_color[k], 0, n * 4, c->alt_stream[k]));
-        HIPCHK(c, hipMemsetAsync(c->alt_depth[k], 0, n * 4, c->alt_stream[k]));
-        HIPCHK(c, hipMemsetAsync(c->alt_hits[k], 0, n * 16, c->alt_stream[k]));
-      }
+    ImageSet &s = c->sets[k];
+    // nothing of the context names set k before it is whole: a failed step leaves cur_set, c->stream and c->d_* as they were, and the
+    // next call tries again
+    if (!s.stream) HIPCHK(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    if (!s.color) {
+      const size_t n = (size_t)c->width * (size_t)c->height;
+      HIPCHK(c, alloc_planes(n, true, s));
+      HIPCHK(c, hipMemsetAsync(s.color, 0, n * 4, s.stream));
+      HIPCHK(c, hipMemsetAsync(s.depth, 0, n * 4, s.stream));
+      HIPCHK(c, hipMemsetAsync(s.hits, 0, n * 16, s.stream));
     }
     // the host runs ahead of the GPU by at most `overlap` frames (a swap chain's depth): the set's previous frame must be complete
     // (the pick launches do not throttle it any more: they need a wave slot, not the frame's turn)
-    if (!c->set_done[k]) HIPCHK(c, hipEventCreateWithFlags(&c->set_done[k], hipEventDisableTiming));
-    if (c->set_used[k]) HIPCHK(c, hipEventSynchronize(c->set_done[k]));
-    c->cur_set = k;
-    c->stream = c->set_stream(k);
-    c->d_color = k ? c->alt_color[k] : c->own_color; c->d_depth = k ? c->alt_depth[k] : c->own_depth; c->d_hits = k ? c->alt_hits[k] : c->own_hits;
-    c->alt_inflight = true;
-    c->pb.in_overlap = true;   // the launch shape of overlapping one-frame launches unless svo_set_tuning named one
-    c->pb.overlap_sets = c->overlap;
+    if (!s.done) HIPCHK(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (s.used) HIPCHK(c, hipEventSynchronize(s.done));
+    c->cur_set = k; c->stream = s.stream;
+    c->d_color = s.color; c->d_depth = s.depth; c->d_hits = s.hits;
+    c->others_inflight = true;
   }
-  int rc = launch_pick(c);
+  Target t = current_target(c);
+  if (overlapped) { t.shape = Target::kOverlap; t.overlap_sets = c->overlap; }   // the launch shape of overlapping one-frame launches
+  int rc = launch_pick(c, t);
   if (rc == SVO_OK) {
-    rc = launch_frame(c, false);
+    rc = launch_frame(c, t, false);
     if (rc) c->pick_live = false;
   }
-  const bool overlapped = c->pb.in_overlap;
-  c->pb.in_overlap = false;
   if (overlapped && rc == SVO_OK) {
-    HIPCHK(c, hipEventRecord(c->set_done[c->cur_set], c->stream));
-    c->set_used[c->cur_set] = true;
+    ImageSet &s = c->sets[c->cur_set];
+    HIPCHK(c, hipEventRecord(s.done, s.stream));
+    s.used = true;
   }
   return rc;
 }
@@ -997,11 +1029,7 @@ int svo_sync(svo_ctx *c) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->alt_inflight) {   // the other sets' frames too
-    HIPCHK(c, hipStreamSynchronize(c->own_stream));
-    for (int k = 1; k < svo_ctx::kMaxSets; k++) if (c->alt_stream[k]) HIPCHK(c, hipStreamSynchronize(c->alt_stream[k]));
-    c->alt_inflight = false;
-  }
+  if (c->others_inflight) return sync_own_streams(c);   // the other sets' frames too
   return SVO_OK;
 }
 
@@ -1009,9 +1037,10 @@ int svo_dispatch(svo_ctx *c) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  int rc = launch_pick(c);
+  const Target t = current_target(c);
+  int rc = launch_pick(c, t);
   if (rc) return rc;
-  rc = launch_frame(c, false);
+  rc = launch_frame(c, t, false);
   if (rc) { c->pick_live = false; return rc; }
   HIPCHK(c, hipEventRecord(c->ev1, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1025,7 +1054,7 @@ int svo_count_frame(svo_ctx *c, svo_stats *out) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   c->pick_live = false;   // (the counting pass renders into the current images)
-  int rc = launch_frame(c, true);
+  int rc = launch_frame(c, current_target(c), true);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   DeviceCounters h;
@@ -1047,15 +1076,16 @@ int svo_time_frames(svo_ctx *c, int warmup, int iters, float *ms) {
   HIPCHK(c, hipSetDevice(c->device));
   c->pick_live = false;
   std::vector<hipEvent_t> ev((size_t)iters + 1, nullptr);
+  const Target t = current_target(c);
   int rc = SVO_OK;
   hipError_t e = hipSuccess;
   const char *what = "";
   auto ok = [&](hipError_t r, const char *w) { if (r != hipSuccess && e == hipSuccess) { e = r; what = w; } return r == hipSuccess; };
-  for (int i = 0; i < warmup && rc == SVO_OK; i++) rc = launch_frame(c, false);
+  for (int i = 0; i < warmup && rc == SVO_OK; i++) rc = launch_frame(c, t, false);
   for (size_t i = 0; i < ev.size() && rc == SVO_OK && e == hipSuccess; i++) ok(hipEventCreate(&ev[i]), "hipEventCreate");
   if (rc == SVO_OK && e == hipSuccess) ok(hipEventRecord(ev[0], c->stream), "hipEventRecord");
   for (int i = 0; i < iters && rc == SVO_OK && e == hipSuccess; i++) {
-    rc = launch_frame(c, false);
+    rc = launch_frame(c, t, false);
     if (rc == SVO_OK) ok(hipEventRecord(ev[(size_t)i + 1], c->stream), "hipEventRecord");
   }
   (void)hipStreamSynchronize(c->stream);   // also on the error paths: the events must be idle before they go
@@ -1100,9 +1130,7 @@ static int ring_create_impl(svo_ctx *c, int slots, int frames_per_slot, int want
                                : hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&s.e0);
     if (e == hipSuccess) e = hipEventCreate(&s.e1);
-    if (e == hipSuccess && own_images) e = hipMalloc((void **)&s.color, n * 4);
-    if (e == hipSuccess && own_images) e = hipMalloc((void **)&s.depth, n * 4);
-    if (e == hipSuccess && own_images && want_hits) e = hipMalloc((void **)&s.hits, n * 16);
+    if (e == hipSuccess && own_images) e = alloc_planes(n, want_hits != 0, s);
     if (e == hipSuccess && own_images) e = hipMemset(s.color, 0, n * 4);
     if (e == hipSuccess && own_images) e = hipMemset(s.depth, 0, n * 4);
     if (e == hipSuccess && own_images && want_hits) e = hipMemset(s.hits, 0, n * 16);
@@ -1152,14 +1180,14 @@ int svo_ring_bind_slot(svo_ctx *c, int slot, void *color, void *depth, void *hit
 // The staged host-to-device copy of a submission's per-frame cameras, on the slot's stream, out of a pinned copy that is
 // rewritten only once the copy that last read it has run.  Called by persist_launch for launches whose cameras do not travel in
 // the table kernel's arguments.  Returns a hipError_t as int.
-static int ring_copy_cams(void *ctx) {
-  svo_ctx *c = (svo_ctx *)ctx;
-  svo_ctx::RingSlot *s = (svo_ctx::RingSlot *)c->batch_cams_slot;
-  if (!s || !c->batch_cams || !s->d_fvar) return (int)hipErrorInvalidValue;
+static int ring_copy_cams(void *target) {
+  const Target *t = (const Target *)target;   // (the slot, the host cameras and their count)
+  svo_ctx::RingSlot *s = t->cams_slot;
+  if (!s || !t->cams || !s->d_fvar) return (int)hipErrorInvalidValue;
   hipError_t e = hipEventSynchronize(s->fvar_copied);
   if (e != hipSuccess) return (int)e;
-  memcpy(s->h_fvar, c->batch_cams, (size_t)c->batch * sizeof(FrameVar));
-  e = hipMemcpyAsync(s->d_fvar, s->h_fvar, (size_t)c->batch * sizeof(FrameVar), hipMemcpyHostToDevice, s->stream);
+  memcpy(s->h_fvar, t->cams, (size_t)t->batch * sizeof(FrameVar));
+  e = hipMemcpyAsync(s->d_fvar, s->h_fvar, (size_t)t->batch * sizeof(FrameVar), hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) e = hipEventRecord(s->fvar_copied, s->stream);
   return (int)e;
 }
@@ -1180,22 +1208,19 @@ static int ring_submit(svo_ctx *c, int frame_number, int nframes, const FrameVar
   const int si = (int)(c->ring_next % (unsigned)c->ring.size());
   svo_ctx::RingSlot &s = c->ring[(size_t)si];
   if (!s.xcolor && !s.color) return fail(c, SVO_E_INVALID, std::string(who) + ": the slot has no images (bind it first)");
-  // the dispatch state of the context, with this slot's stream, images and frame range swapped in
-  struct Saved {
-    hipStream_t stream; uint32_t *col; float *dep; uint4 *hit; bool ext; int batch; uint64_t stride; int frame; float cam[15];
-  } sv = {c->stream, c->d_color, c->d_depth, c->d_hits, c->external_outputs, c->batch, c->frame_stride, c->frame_number, {}};
-  memcpy(sv.cam, c->cam, sizeof sv.cam);
-  c->stream = s.stream;
-  c->external_outputs = true;
-  if (s.xcolor) { c->d_color = (uint32_t *)s.xcolor; c->d_depth = (float *)s.xdepth; c->d_hits = (uint4 *)s.xhits; c->frame_stride = s.xstride; }
-  else { c->d_color = s.color; c->d_depth = s.depth; c->d_hits = s.hits; c->frame_stride = c->ring_stride; }
-  c->batch = nframes;
-  c->frame_number = frame_number;
+  // the launch's target: this slot's stream, images and frame range; the context's own dispatch state is not touched
+  Target t;
+  t.stream = s.stream; t.external = true; t.batch = nframes; t.frame_number = frame_number;
+  if (s.xcolor) { t.out.color = (uint32_t *)s.xcolor; t.out.depth = (float *)s.xdepth; t.out.hits = (uint4 *)s.xhits; t.frame_stride = s.xstride; }
+  else { t.out = s; t.frame_stride = c->ring_stride; }
+  memcpy(t.cam, c->cam, sizeof t.cam);
+  // the launch shape a ring of several slots gets unless svo_set_tuning named one: kRingWavesPerCu persistent waves per CU
+  if (c->ring.size() > 1) t.shape = Target::kRing;
   int rc = SVO_OK;
   hipError_t e = hipSuccess;
   if (cams && nframes == 1) {           // one frame: simply this frame's camera (beam pre-pass and all)
-    memcpy(c->cam, cams[0].cam, sizeof c->cam);
-    c->frame_number = cams[0].frame_number;
+    memcpy(t.cam, cams[0].cam, sizeof t.cam);
+    t.frame_number = cams[0].frame_number;
   } else if (cams) {
     // the batch's cameras live in the slot's table on the device.  Launches with row / column tables carry them there inside the
     // table kernel's arguments (up to kCamPack frames); the others get the staged copy of ring_copy_cams, enqueued by the
@@ -1206,14 +1231,11 @@ static int ring_submit(svo_ctx *c, int frame_number, int nframes, const FrameVar
       if (e == hipSuccess) e = hipEventCreateWithFlags(&s.fvar_copied, hipEventDisableTiming);
       if (e == hipSuccess) e = hipEventRecord(s.fvar_copied, s.stream);   // (so that the first wait below has something to wait for)
     }
-    c->batch_cams = cams; c->batch_cams_dev = s.d_fvar; c->batch_cams_slot = &s;
-    c->frame_number = cams[0].frame_number;
+    t.cams = cams; t.cams_slot = &s;
+    t.frame_number = cams[0].frame_number;
   }
   if (e == hipSuccess) e = hipEventRecord(s.e0, s.stream);
-  // the launch shape a ring of several slots gets unless svo_set_tuning named one: kRingWavesPerCu persistent waves per CU
-  c->pb.in_ring = c->ring.size() > 1;
-  if (e == hipSuccess) rc = launch_frame(c, false);
-  c->pb.in_ring = false;
+  if (e == hipSuccess) rc = launch_frame(c, t, false);
   if (e == hipSuccess && rc == SVO_OK) e = hipEventRecord(s.e1, s.stream);
   if (e == hipSuccess && rc == SVO_OK && s.fwd_dst) {
     // the slot's frames travel to the frame owner behind the launch, on the same stream: a device-to-device copy (SDMA
@@ -1228,10 +1250,6 @@ static int ring_submit(svo_ctx *c, int frame_number, int nframes, const FrameVar
     }
     if (e == hipSuccess && s.e2) e = hipEventRecord(s.e2, s.stream);
   }
-  c->stream = sv.stream; c->d_color = sv.col; c->d_depth = sv.dep; c->d_hits = sv.hit; c->external_outputs = sv.ext;
-  c->batch = sv.batch; c->frame_stride = sv.stride; c->frame_number = sv.frame;
-  memcpy(c->cam, sv.cam, sizeof c->cam);
-  c->batch_cams = nullptr; c->batch_cams_dev = nullptr; c->batch_cams_slot = nullptr;
   if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
   if (rc) return rc;
   s.first_frame = cams ? cams[0].frame_number : frame_number; s.nframes = nframes; s.used = true;

@@ -309,8 +309,8 @@ class Renderer {
   void readDepth(float *d) { if (ensure()) check(svo_read_depth(ctx, d)); }
   void readHits(svo_hit *h) { if (ensure()) check(svo_read_hits(ctx, h)); }
   // the crosshair pick of Main.updateEarly (Main.java:132-146) without the full-frame read-back.  At the pick position
-  // (setPick; default the image centre = Main's crosshair) the value comes from pinned host memory as soon as the lane that
-  // renders the pixel has stored it -- the frame need not have ended (round 6); anywhere else it waits for the frame.
+  // (setPick; default the image centre = Main's crosshair) the value comes from pinned host memory as soon as the frame's pick
+  // launch (one wave, in front of the frame's kernels) has stored it -- the frame need not have ended (round 6); anywhere else it waits for the frame.
   float readDepthPixel(int x, int y) { float d = 0.0f; if (ensure()) check(svo_read_pixel(ctx, x, y, nullptr, &d, nullptr)); return d; }
   void setPick(int x, int y) { if (ensure()) check(svo_set_pick(ctx, x, y)); }          // x < 0: no pick, every read-back waits
   void setOverlap(int sets) { if (ensure()) check(svo_set_overlap(ctx, sets)); }   // {stream, image} sets dispatchCompute takes turns on: 0 = one, 1 = default (4), 2 .. 8

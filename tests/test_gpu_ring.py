@@ -417,3 +417,107 @@ def test_a_continued_accumulation_is_refused_on_a_ring_of_several_slots(ctx):
         ctx.set_progressive(False)
         ctx.set_sequence(1, False)
         ctx.ring_destroy()
+
+
+# ---- a ring submission names its own launch target: the context's dispatch state (stream, images, camera, frame number)
+# is not part of it.  64 x 40, camera K2 and frame 5 on the context, a ring of 2 slots x 2 frames.
+W0, H0 = 64, 40
+
+
+@pytest.fixture(scope="module")
+def plain_k2_frame5():
+    """camera K2, frame 5, mode 0 on a context that never had a ring"""
+    import svo_raytracer_amd.scene as scene
+    from svo_raytracer_amd import hiplib
+    from svo_raytracer_amd.cameras import CAMERAS
+    c = hiplib.HipContext(0)
+    try:
+        return c.render(scene.build_scene(256)[0], W0, H0, CAMERAS["K2"], 5, 0)
+    finally:
+        c.close()
+
+
+def _context_with_ring(ctx):
+    from svo_raytracer_amd.cameras import CAMERAS
+    ctx.set_pipeline(1)
+    ctx.resize(W0, H0)
+    ctx.set_camera(CAMERAS["K2"])
+    ctx.set_params(5, 0, 0, 0, 2, 0, 1)
+    ctx.ring_create(2, 2, want_hits=True)
+    return ctx.output_device_ptrs()
+
+
+def _dispatch_and_read(ctx):
+    ctx.dispatch()
+    return {"rgba": ctx.read_color(), "depth": ctx.read_depth(), "hits": ctx.read_hits()}
+
+
+def test_a_ring_submission_leaves_the_contexts_dispatch_state_alone(ctx, plain_k2_frame5):
+    from svo_raytracer_amd.cameras import CAMERAS
+    before = _context_with_ring(ctx)
+    try:
+        assert all(before)
+        ctx.ring_submit_cams(np.stack([CAMERAS["K0"], CAMERAS["K1"]]), [9, 1])
+        assert ctx.output_device_ptrs() == before
+        _eq(_dispatch_and_read(ctx), plain_k2_frame5)
+        assert ctx.output_device_ptrs() == before
+    finally:
+        ctx.ring_destroy()
+        ctx.set_camera(CAMERAS["K1"])
+
+
+def test_a_refused_ring_submission_leaves_the_contexts_dispatch_state_alone(ctx, plain_k2_frame5):
+    from svo_raytracer_amd.cameras import CAMERAS
+    from svo_raytracer_amd.hiplib import SvoError
+    two = np.stack([CAMERAS["K0"], CAMERAS["K1"]])
+    before = _context_with_ring(ctx)
+    try:
+        with pytest.raises(SvoError):
+            ctx.ring_submit(2, 3)                        # more frames than a slot holds
+        _eq(_dispatch_and_read(ctx), plain_k2_frame5)
+        assert ctx.output_device_ptrs() == before
+        ctx.set_params(5, 0, 0, 1, 2, 0, 1)
+        with pytest.raises(SvoError):
+            ctx.ring_submit_cams(two, [9, 1])            # two cameras and the beam pre-pass
+        ctx.set_params(5, 0, 0, 0, 2, 0, 1)
+        _eq(_dispatch_and_read(ctx), plain_k2_frame5)
+        assert ctx.output_device_ptrs() == before
+        ctx.set_progressive(True)
+        ctx.set_sequence(1, False)
+        with pytest.raises(SvoError, match="ONE slot"):
+            ctx.ring_submit(2, 1)                        # a continued accumulation on two slots
+        ctx.set_progressive(False)
+        _eq(_dispatch_and_read(ctx), plain_k2_frame5)
+        assert ctx.output_device_ptrs() == before
+    finally:
+        ctx.set_progressive(False)
+        ctx.set_sequence(1, False)
+        ctx.set_params(5, 0, 0, 0, 2, 0, 1)
+        ctx.ring_destroy()
+        ctx.set_camera(CAMERAS["K1"])
+
+
+def test_overlapped_dispatches_and_ring_submissions_interleaved(ctx):
+    """svo_dispatch_async on three image sets, a ring submission after each: every read-back sees the frame of the last
+    dispatch, every slot keeps the frames of its last submission."""
+    ctx.set_pipeline(1)
+    ctx.resize(W0, H0)
+    want = {f: _alone(ctx, W0, H0, f, 0) for f in (2, 3, 4, 5) + tuple(range(10, 18))}
+    ctx.set_overlap(3)
+    try:
+        ctx.ring_create(2, 2, want_hits=True)
+        held = {}
+        for i, f in enumerate((2, 3, 4, 5)):
+            ctx.set_params(f, 0, 0, 0, 2, 0, 1)
+            ctx.dispatch_async()
+            assert (ctx.read_color() == want[f]["rgba"]).all()
+            held[ctx.ring_submit(10 + 2 * i, 2)] = 10 + 2 * i
+            assert (ctx.read_color() == want[f]["rgba"]).all()      # ... and still after the submission
+        ctx.sync()
+        assert sorted(held) == [0, 1]
+        for s, first in held.items():
+            for k in range(2):
+                _eq(ctx.ring_read(s, k, want_hits=True), want[first + k])
+    finally:
+        ctx.ring_destroy()
+        ctx.set_overlap(1)

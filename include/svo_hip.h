@@ -90,6 +90,10 @@ int svo_pool_upload(svo_ctx *ctx, const void *host, uint64_t nbytes);
 int svo_pool_update(svo_ctx *ctx, const void *host_base, uint64_t start, uint64_t end);
 /* replaces Renderer.getSSBO: glGetBufferSubData (Renderer.java:148-150) */
 int svo_pool_download(svo_ctx *ctx, void *host, uint64_t nbytes);
+/* the mirror of svo_pool_update: bytes [start, end) of the device pool to host_base + start, so that a host that keeps
+ * its own copy of the pool stays in step with strokes made on the device (svo_brush_*).  host_base points at byte 0.
+ * SVO_E_INVALID unless start < end <= the pool's length. */
+int svo_pool_download_range(svo_ctx *ctx, void *host_base, uint64_t start, uint64_t end);
 /* device-side view of the pool, for a multi-GPU broadcast straight into it (RCCL);
  * svo_pool_reserve allocates without uploading. */
 int svo_pool_reserve(svo_ctx *ctx, uint64_t nbytes);
@@ -226,6 +230,28 @@ int svo_derived_read(svo_ctx *ctx, uint64_t first, uint64_t count, void *desc, v
  * updates followed that way so far, and of the last one: *states recomputed, *added descriptors, GPU
  * time.  Any may be NULL. */
 int svo_derived_refresh_info(svo_ctx *ctx, uint64_t *refreshes, uint64_t *states, uint64_t *added, float *gpu_ms);
+
+/* ---- SDF brush strokes on the device pool ------------------------------------------ */
+/* replaces Octree.useSDFBrush(new Sphere(origin, radius), value) + the two Renderer.updateSSBO calls of Main.placeSDF
+ * (Main.java:338-353; Octree.java:672-885, sdf/Sphere.java): the stroke is applied to the pool the context holds, no
+ * host copy needed.  world_size = 0 means Constants.WORLD_SIZE (8196, sic; at most 32768), max_lod = 0 means 13.
+ * cb (may be NULL) receives the reference's ChangeBounds {start0, end0, start1, end1}: [start1, end1) are the appended
+ * records (end1 is the pool's new length).  After the call the pool, its length and cb are byte for byte what the
+ * reference's sequential recursion leaves on a proper tree (builder output and earlier strokes).  Like every pool
+ * mutator the call waits for the whole device first; a walkable descriptor table follows the stroke as it follows
+ * svo_pool_update.  The stroke is planned before anything is written: on any failure -- value outside 0..255, a record
+ * pointer outside the pool (SVO_E_INVALID), too many visited nodes or a result of 2^31 bytes (SVO_E_TOOLARGE), no pool
+ * (SVO_E_NOPOOL) -- the pool, its length and the table are as they were. */
+int svo_brush_sphere(svo_ctx *ctx, const int origin[3], int radius, int value, int world_size, int max_lod, int32_t cb[4]);
+/* the same with new Box(origin, w, h, d) (Main.java:244-249, sdf/Box.java: the distance subtracts the full extents) */
+int svo_brush_box(svo_ctx *ctx, const int origin[3], int w, int h, int d, int value, int world_size, int max_lod, int32_t cb[4]);
+/* what the strokes did: *strokes made so far, and of the last one the nodes *visited, the nodes *subdivided, the GPU
+ * time of planning and writing it, and [*lo, *hi): the lowest and the highest + 1 byte it wrote below start1 (lo = hi = 0:
+ * none).  The DELETE_VALUE (127) marks on a filled node's children are not counted by the reference's
+ * updateExistingNodeBounds and can lie outside [start0, end0): a host that mirrors the pool downloads [lo, hi) and
+ * [start1, end1), not cb's first range.  Any may be NULL. */
+int svo_brush_info(svo_ctx *ctx, uint64_t *strokes, uint64_t *visited, uint64_t *subdivided, uint64_t *lo, uint64_t *hi, float *gpu_ms);
+
 /* record per-pixel svo_hit (costs 16 B/pixel of stores); default on */
 int svo_set_hit_records(svo_ctx *ctx, int enabled);
 
@@ -370,6 +396,9 @@ svo_ctx *svo_group_member(svo_group *g, int i);
 int svo_group_pool_upload(svo_group *g, const void *host, uint64_t nbytes);
 int svo_group_pool_update(svo_group *g, const void *host_base, uint64_t start, uint64_t end);
 int svo_group_pool_download(svo_group *g, void *host, uint64_t nbytes);
+/* svo_brush_sphere / svo_brush_box on every member's replica of the pool (the same bytes and the same cb on each) */
+int svo_group_brush_sphere(svo_group *g, const int origin[3], int radius, int value, int world_size, int max_lod, int32_t cb[4]);
+int svo_group_brush_box(svo_group *g, const int origin[3], int w, int h, int d, int value, int world_size, int max_lod, int32_t cb[4]);
 int svo_group_build_from_heightmap(svo_group *g, const uint16_t *height, const uint8_t *material, int n, uint64_t *out_nbytes);
 int svo_group_set_camera(svo_group *g, const float pos[3], const float l1[3], const float l2[3], const float r1[3], const float r2[3]);
 int svo_group_set_params(svo_group *g, int frame_number, int render_mode, int buffer_end, int use_beam, int bounces,

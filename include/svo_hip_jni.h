@@ -33,6 +33,22 @@ jint Java_src_engine_HipRenderer_nPoolUpload(void *env, void *cls, jlong ctx, jl
 jint Java_src_engine_HipRenderer_nPoolUpdate(void *env, void *cls, jlong ctx, jlong base_addr, jlong start, jlong end);
 /* Renderer.getSSBO (Renderer.java:148-150) */
 jint Java_src_engine_HipRenderer_nPoolDownload(void *env, void *cls, jlong ctx, jlong addr, jlong nbytes);
+/* svo_pool_download_range: bytes [start, end) of the device pool to base_addr + start (a host copy kept in step) */
+jint Java_src_engine_HipRenderer_nPoolDownloadRange(void *env, void *cls, jlong ctx, jlong base_addr, jlong start, jlong end);
+/* Octree.useSDFBrush(new Sphere / new Box, value) + the two updateSSBO calls of Main.placeSDF (Main.java:338-353) on the
+ * device pool; cb_addr: 4 ints {start0, end0, start1, end1} (ChangeBounds), 0 = not wanted */
+jint Java_src_engine_HipRenderer_nBrushSphere(void *env, void *cls, jlong ctx, jint ox, jint oy, jint oz, jint radius, jint value,
+                                              jint world_size, jint max_lod, jlong cb_addr);
+jint Java_src_engine_HipRenderer_nBrushBox(void *env, void *cls, jlong ctx, jint ox, jint oy, jint oz, jint w, jint h, jint d,
+                                           jint value, jint world_size, jint max_lod, jlong cb_addr);
+/* svo_brush_info: returns the strokes made so far (or a negative status); counts_addr: 4 longs {visited, subdivided, lo,
+ * hi} of the last one, ms_addr: 1 float (its GPU time); 0 = not wanted */
+jlong Java_src_engine_HipRenderer_nBrushInfo(void *env, void *cls, jlong ctx, jlong counts_addr, jlong ms_addr);
+/* the stroke on every member's replica (svo_group_brush_*) */
+jint Java_src_engine_HipRenderer_nGroupBrushSphere(void *env, void *cls, jlong g, jint ox, jint oy, jint oz, jint radius, jint value,
+                                                   jint world_size, jint max_lod, jlong cb_addr);
+jint Java_src_engine_HipRenderer_nGroupBrushBox(void *env, void *cls, jlong g, jint ox, jint oy, jint oz, jint w, jint h, jint d,
+                                                jint value, jint world_size, jint max_lod, jlong cb_addr);
 /* glUniform3fv(8 | 1..4) (Main.java:269-273) */
 jint Java_src_engine_HipRenderer_nSetCamera(void *env, void *cls, jlong ctx, jfloat px, jfloat py, jfloat pz,
                                             jfloat l1x, jfloat l1y, jfloat l1z, jfloat l2x, jfloat l2y, jfloat l2z,

@@ -133,6 +133,62 @@ public class HipRenderer {
     check(nPoolDownload(ctx, MemoryUtil.memAddress(buffer), buffer.remaining()));
   }
 
+  /** svo_pool_download_range: bytes [start, end) of the device pool into `data` (whose byte 0 is the pool's byte 0). */
+  public void getSSBO(ByteBuffer data, long start, long end) {
+    if (start < end)
+      check(nPoolDownloadRange(ctx, MemoryUtil.memAddress0(data), start, end));
+  }
+
+  /**
+   * Octree.useSDFBrush(new Sphere(origin, radius), value) and the two Renderer.updateSSBO calls of Main.placeSDF
+   * (Main.java:338-353) on the device pool: returns ChangeBounds {start0, end0, start1, end1}; end1 is the pool's new
+   * length.  worldSize 0 = Constants.WORLD_SIZE, maxLOD 0 = 13.
+   */
+  public int[] brushSphere(int ox, int oy, int oz, int radius, int value, int worldSize, int maxLOD) {
+    ByteBuffer cb = MemoryUtil.memAlloc(16);
+    check(nBrushSphere(ctx, ox, oy, oz, radius, value, worldSize, maxLOD, MemoryUtil.memAddress(cb)));
+    int[] out = {cb.getInt(0), cb.getInt(4), cb.getInt(8), cb.getInt(12)};
+    MemoryUtil.memFree(cb);
+    return out;
+  }
+
+  /** The same with new Box(origin, w, h, d) (Main.java:244-249). */
+  public int[] brushBox(int ox, int oy, int oz, int w, int h, int d, int value, int worldSize, int maxLOD) {
+    ByteBuffer cb = MemoryUtil.memAlloc(16);
+    check(nBrushBox(ctx, ox, oy, oz, w, h, d, value, worldSize, maxLOD, MemoryUtil.memAddress(cb)));
+    int[] out = {cb.getInt(0), cb.getInt(4), cb.getInt(8), cb.getInt(12)};
+    MemoryUtil.memFree(cb);
+    return out;
+  }
+
+  /**
+   * svo_brush_info: {strokes so far, nodes visited, nodes subdivided, lo, hi} of the last stroke.  [lo, hi) are the bytes
+   * it wrote below start1 (the DELETE_VALUE marks included, which ChangeBounds' first range can miss).
+   */
+  public long[] brushInfo() {
+    ByteBuffer counts = MemoryUtil.memAlloc(32);
+    long strokes = nBrushInfo(ctx, MemoryUtil.memAddress(counts), 0L);
+    long[] out = {strokes, counts.getLong(0), counts.getLong(8), counts.getLong(16), counts.getLong(24)};
+    MemoryUtil.memFree(counts);
+    return out;
+  }
+
+  /**
+   * Main.placeSDF (Main.java:338-353) with the stroke on the GPU: the brush, its time, and -- for a host that keeps its own
+   * copy of the pool (`mirror`, may be null) -- the two byte ranges the other way round.
+   */
+  public int[] placeSDF(int ox, int oy, int oz, int radius, int value, ByteBuffer mirror) {
+    long t0 = System.currentTimeMillis();
+    int[] cb = brushSphere(ox, oy, oz, radius, value, 0, 0);
+    System.out.println("SDF brush took " + (System.currentTimeMillis() - t0) + "ms");
+    if (mirror != null) {
+      long[] info = brushInfo();
+      getSSBO(mirror, info[3], info[4]);
+      getSSBO(mirror, cb[2], cb[3]);
+    }
+    return cb;
+  }
+
   public Shader getShaderByName(String name) {
     for (Shader shader : shaders) {
       if (shader.name.equals(name))
@@ -494,6 +550,32 @@ public class HipRenderer {
       check(nGroupPoolUpdate(g, MemoryUtil.memAddress0(data), start, end));
     }
 
+    /** HipRenderer.brushSphere on every GPU's replica of the pool. */
+    public int[] brushSphere(int ox, int oy, int oz, int radius, int value, int worldSize, int maxLOD) {
+      ByteBuffer cb = MemoryUtil.memAlloc(16);
+      check(nGroupBrushSphere(g, ox, oy, oz, radius, value, worldSize, maxLOD, MemoryUtil.memAddress(cb)));
+      int[] out = {cb.getInt(0), cb.getInt(4), cb.getInt(8), cb.getInt(12)};
+      MemoryUtil.memFree(cb);
+      return out;
+    }
+
+    /** HipRenderer.brushBox on every GPU's replica of the pool. */
+    public int[] brushBox(int ox, int oy, int oz, int w, int h, int d, int value, int worldSize, int maxLOD) {
+      ByteBuffer cb = MemoryUtil.memAlloc(16);
+      check(nGroupBrushBox(g, ox, oy, oz, w, h, d, value, worldSize, maxLOD, MemoryUtil.memAddress(cb)));
+      int[] out = {cb.getInt(0), cb.getInt(4), cb.getInt(8), cb.getInt(12)};
+      MemoryUtil.memFree(cb);
+      return out;
+    }
+
+    /** Main.placeSDF (Main.java:338-353) with the stroke made on every GPU. */
+    public int[] placeSDF(int ox, int oy, int oz, int radius, int value) {
+      long t0 = System.currentTimeMillis();
+      int[] cb = brushSphere(ox, oy, oz, radius, value, 0, 0);
+      System.out.println("SDF brush took " + (System.currentTimeMillis() - t0) + "ms");
+      return cb;
+    }
+
     public void setImageSize(int width, int height) {
       check(nGroupResize(g, width, height));
     }
@@ -606,6 +688,12 @@ public class HipRenderer {
   private static native int nPoolUpload(long ctx, long addr, long nbytes);
   private static native int nPoolUpdate(long ctx, long baseAddr, long start, long end);
   private static native int nPoolDownload(long ctx, long addr, long nbytes);
+  private static native int nPoolDownloadRange(long ctx, long baseAddr, long start, long end);
+  private static native int nBrushSphere(long ctx, int ox, int oy, int oz, int radius, int value, int worldSize, int maxLOD,
+      long cbAddr);
+  private static native int nBrushBox(long ctx, int ox, int oy, int oz, int w, int h, int d, int value, int worldSize,
+      int maxLOD, long cbAddr);
+  private static native long nBrushInfo(long ctx, long countsAddr, long msAddr);
   private static native int nSetCamera(long ctx, float px, float py, float pz, float l1x, float l1y, float l1z,
       float l2x, float l2y, float l2z, float r1x, float r1y, float r1z, float r2x, float r2y, float r2z);
   private static native int nSetParams(long ctx, int frameNumber, int renderMode, int bufferEnd, int useBeam,
@@ -658,6 +746,10 @@ public class HipRenderer {
   private static native long nGroupMember(long g, int i);
   private static native int nGroupPoolUpload(long g, long addr, long nbytes);
   private static native int nGroupPoolUpdate(long g, long baseAddr, long start, long end);
+  private static native int nGroupBrushSphere(long g, int ox, int oy, int oz, int radius, int value, int worldSize, int maxLOD,
+      long cbAddr);
+  private static native int nGroupBrushBox(long g, int ox, int oy, int oz, int w, int h, int d, int value, int worldSize,
+      int maxLOD, long cbAddr);
   private static native int nGroupSetCamera(long g, long cam15Addr);
   private static native int nGroupSetParams(long g, int frameNumber, int renderMode, int bufferEnd, int useBeam, int bounces,
       int mirrorMask, int spp);

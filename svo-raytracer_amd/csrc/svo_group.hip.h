@@ -212,6 +212,15 @@ int svo_group_pool_update(svo_group *g, const void *host_base, uint64_t start, u
   if (!g) return SVO_E_INVALID;
   GALL(g, svo_pool_update(c, host_base, start, end));   // two small byte ranges per brush stroke: from the host to every member
 }
+// the stroke on every member's replica: the same pool, the same arguments, the same bytes and bounds
+int svo_group_brush_sphere(svo_group *g, const int origin[3], int radius, int value, int world_size, int max_lod, int32_t cb[4]) {
+  if (!g) return SVO_E_INVALID;
+  GALL(g, svo_brush_sphere(c, origin, radius, value, world_size, max_lod, cb));
+}
+int svo_group_brush_box(svo_group *g, const int origin[3], int w, int h, int d, int value, int world_size, int max_lod, int32_t cb[4]) {
+  if (!g) return SVO_E_INVALID;
+  GALL(g, svo_brush_box(c, origin, w, h, d, value, world_size, max_lod, cb));
+}
 int svo_group_build_from_heightmap(svo_group *g, const uint16_t *height, const uint8_t *material, int n, uint64_t *out_nbytes) {
   if (!g) return SVO_E_INVALID;
   int rc = gmember(g, 0, svo_build_from_heightmap(g->m[0], height, material, n, out_nbytes));

@@ -31,6 +31,7 @@
 #include "svo_build.hip.h"
 #include "svo_beam.hip.h"
 #include "svo_derive.hip.h"
+#include "svo_brush.hip.h"
 
 using namespace svo;
 
@@ -114,6 +115,7 @@ struct svo_ctx {
   WavefrontBuffers wf;
 #endif
   PersistBuffers pb;
+  brush::State bs;             // work items and counters of svo_brush_* (made at the first stroke), what the last stroke did
   // frames in flight behind the boundary (svo_ring_*): per slot a stream of its own, output buffers for up to
   // ring_frames consecutive frames, and the events around its last submission
   struct RingSlot : Planes {        // (the planes: library-owned images, frame after frame)
@@ -288,6 +290,7 @@ int svo_destroy(svo_ctx *c) {
   for (auto &e : c->beam_done) if (e) (void)hipEventDestroy(e);
   if (c->d_beam_live) (void)hipFree(c->d_beam_live);
   derive::free_table(c->dt);
+  brush::free_state(c->bs);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   ring_free(c);
@@ -435,6 +438,120 @@ int svo_pool_commit(svo_ctx *c) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());   // the caller's writes (any stream) and every frame in flight
   return refresh_dword0(c);
+}
+
+int svo_pool_download_range(svo_ctx *c, void *host_base, uint64_t start, uint64_t end) {
+  if (!c || !host_base) return fail(c, SVO_E_INVALID, "svo_pool_download_range: null buffer");
+  if (!c->d_pool) return fail(c, SVO_E_NOPOOL, "no pool");
+  if (start >= end || end > c->pool_len) return fail(c, SVO_E_INVALID, "svo_pool_download_range: need start < end <= the pool's length");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy((uint8_t *)host_base + start, c->d_pool + start, end - start, hipMemcpyDeviceToHost));
+  return SVO_OK;
+}
+
+// ---------------------------------------------------------------- SDF brush (svo_brush.hip.h)
+// Main.placeSDF (Main.java:338-353) without the host: plan on the device, grow the pool once, write, let the table follow
+static int brush_stroke(svo_ctx *c, const brush::Sdf &s, int value, int world_size, int max_lod, int32_t cb[4], const char *who) {
+  if (world_size == 0) world_size = 8196;   // Constants.WORLD_SIZE (sic)
+  if (max_lod == 0) max_lod = 13;
+  if (value < 0 || value > 255) return fail(c, SVO_E_INVALID, std::string(who) + ": value must be a byte (0..255)");
+  if (world_size < 1 || world_size > brush::kMaxWorld || max_lod < 1 || max_lod > 15)
+    return fail(c, SVO_E_INVALID, std::string(who) + ": world_size 1..32768 and max_lod 1..15");
+  for (int i = 0; i < 3; i++)
+    if (s.o[i] < -(1 << 20) || s.o[i] > (1 << 20)) return fail(c, SVO_E_INVALID, std::string(who) + ": origin out of range");
+  if (!c->d_pool || c->pool_len < 7) return fail(c, SVO_E_NOPOOL, std::string(who) + ": no pool uploaded");
+  const bool had_table = c->derived_valid && c->dt.ok;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());   // see svo_pool_upload
+  hipStream_t st = c->sets[0].stream;
+  brush::State &b = c->bs;
+  if (!b.ctr) HIPCHK(c, hipMalloc((void **)&b.ctr, brush::kCtrWords * sizeof(uint32_t)));
+  if (!b.e0) HIPCHK(c, hipEventCreate(&b.e0));
+  if (!b.e1) HIPCHK(c, hipEventCreate(&b.e1));
+  const uint32_t start1 = (uint32_t)c->pool_len;
+  HIPCHK(c, hipEventRecord(b.e0, st));
+  brush::Plan p;
+  for (;;) {
+    if (!b.items) {
+      if (!b.cap) b.cap = brush::kFirstCap;
+      hipError_t e = hipMalloc((void **)&b.items, (size_t)b.cap * sizeof(brush::Item));
+      if (e != hipSuccess) { b.items = nullptr; b.cap = 0; return fail(c, SVO_E_HIP, std::string(who) + ": work items: " + hipGetErrorString(e)); }
+    }
+    p = brush::Plan();
+    hipError_t e = brush::plan(b, c->d_pool, start1, s, value, world_size, max_lod, st, p);
+    if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    if (!(p.flags & brush::kFlagItems)) break;
+    if (b.cap >= brush::kLastCap) return fail(c, SVO_E_TOOLARGE, std::string(who) + ": the stroke visits more nodes than the work lists hold");
+    HIPCHK(c, hipFree(b.items));   // the plan wrote nothing but its items: again, with four times the room
+    b.items = nullptr;
+    b.cap *= 4;
+  }
+  if (p.flags & brush::kFlagBounds) return fail(c, SVO_E_INVALID, std::string(who) + ": a record the stroke reaches lies outside the pool");
+  if (p.flags & brush::kFlagShortLeaf)
+    return fail(c, SVO_E_INVALID, std::string(who) + ": the stroke would subdivide a 3-byte or 1-byte leaf (max_lod does not match the tree)");
+  const uint64_t new_len = (uint64_t)start1 + p.appended;
+  int rc = ensure_pool_capacity(c, new_len, true);   // SVO_E_TOOLARGE from 2^31 bytes on; the pool as it was
+  if (rc) return rc;
+  // from here on the pool changes
+  pool_changed(c);
+  hipLaunchKernelGGL(brush::write_kernel, dim3((p.items + 255u) / 256u), dim3(256), 0, st, c->d_pool, start1, b.items, p.items, value, b.ctr);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(b.e1, st));
+  uint32_t h[brush::kCtrWords];
+  HIPCHK(c, hipMemcpyAsync(h, b.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->pool_len = new_len;
+  const uint32_t lo = h[brush::kCtrHi] ? h[brush::kCtrLo] : 0u, hi = h[brush::kCtrHi];
+  if (cb) { cb[0] = (int32_t)h[brush::kCtrStart0]; cb[1] = (int32_t)h[brush::kCtrEnd0]; cb[2] = (int32_t)start1; cb[3] = (int32_t)new_len; }
+  b.strokes++; b.visited = p.items; b.subdivided = h[brush::kCtrSubdivided]; b.lo = lo; b.hi = hi;
+  (void)hipEventElapsedTime(&b.gpu_ms, b.e0, b.e1);
+  if (hi > lo && lo < 4) { rc = refresh_dword0(c); if (rc) return rc; }
+  if (had_table) {
+    // what the two svo_pool_update calls of the host route do: the table follows [lo, hi) and [start1, end1)
+    bool refreshed = true;
+    const uint64_t ranges[2][2] = {{lo, hi}, {start1, new_len}};
+    for (int k = 0; k < 2 && refreshed; k++) {
+      if (ranges[k][0] >= ranges[k][1]) continue;
+      hipError_t e = derive::refresh_table(c->dt, c->d_pool, c->pool_len, ranges[k][0], ranges[k][1], st, &refreshed);
+      if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("descriptor table refresh: ") + hipGetErrorString(e));
+    }
+    c->derived_valid = refreshed;   // false: the next dispatch builds it anew
+  }
+  return SVO_OK;
+}
+
+int svo_brush_sphere(svo_ctx *c, const int origin[3], int radius, int value, int world_size, int max_lod, int32_t cb[4]) {
+  if (!c || !origin) return fail(c, SVO_E_INVALID, "svo_brush_sphere: null origin");
+  if (radius < 0 || radius > (1 << 20)) return fail(c, SVO_E_INVALID, "svo_brush_sphere: radius out of range");
+  brush::Sdf s{};
+  s.kind = 0; s.r = radius;
+  for (int i = 0; i < 3; i++) { s.o[i] = origin[i]; s.mn[i] = origin[i] - radius - 1; s.mx[i] = origin[i] + radius + 1; }   // Sphere.java
+  return brush_stroke(c, s, value, world_size, max_lod, cb, "svo_brush_sphere");
+}
+
+int svo_brush_box(svo_ctx *c, const int origin[3], int w, int h, int d, int value, int world_size, int max_lod, int32_t cb[4]) {
+  if (!c || !origin) return fail(c, SVO_E_INVALID, "svo_brush_box: null origin");
+  const int ext[3] = {w, h, d};
+  brush::Sdf s{};
+  s.kind = 1;
+  for (int i = 0; i < 3; i++) {
+    if (ext[i] < 0 || ext[i] > (1 << 20)) return fail(c, SVO_E_INVALID, "svo_brush_box: extent out of range");
+    const int half = (ext[i] + 1) / 2;   // (int)Math.ceil(w / 2.0f), Box.java
+    s.o[i] = origin[i]; s.b[i] = ext[i]; s.mn[i] = origin[i] - half; s.mx[i] = origin[i] + half;
+  }
+  return brush_stroke(c, s, value, world_size, max_lod, cb, "svo_brush_box");
+}
+
+int svo_brush_info(svo_ctx *c, uint64_t *strokes, uint64_t *visited, uint64_t *subdivided, uint64_t *lo, uint64_t *hi, float *gpu_ms) {
+  if (!c) return SVO_E_INVALID;
+  if (strokes) *strokes = c->bs.strokes;
+  if (visited) *visited = c->bs.visited;
+  if (subdivided) *subdivided = c->bs.subdivided;
+  if (lo) *lo = c->bs.lo;
+  if (hi) *hi = c->bs.hi;
+  if (gpu_ms) *gpu_ms = c->bs.gpu_ms;
+  return SVO_OK;
 }
 
 // ---------------------------------------------------------------- world generation

@@ -23,6 +23,27 @@ jint Java_src_engine_HipRenderer_nPoolUpdate(void *, void *, jlong ctx, jlong ba
 jint Java_src_engine_HipRenderer_nPoolDownload(void *, void *, jlong ctx, jlong addr, jlong nbytes) {
   return svo_pool_download((svo_ctx *)(intptr_t)ctx, (void *)(intptr_t)addr, (uint64_t)nbytes);
 }
+jint Java_src_engine_HipRenderer_nPoolDownloadRange(void *, void *, jlong ctx, jlong base, jlong start, jlong end) {
+  if (start < 0 || end < 0) return SVO_E_INVALID;
+  return svo_pool_download_range((svo_ctx *)(intptr_t)ctx, (void *)(intptr_t)base, (uint64_t)start, (uint64_t)end);
+}
+jint Java_src_engine_HipRenderer_nBrushSphere(void *, void *, jlong ctx, jint ox, jint oy, jint oz, jint radius, jint value,
+                                              jint world_size, jint max_lod, jlong cb_addr) {
+  const int org[3] = {ox, oy, oz};
+  return svo_brush_sphere((svo_ctx *)(intptr_t)ctx, org, radius, value, world_size, max_lod, (int32_t *)(intptr_t)cb_addr);
+}
+jint Java_src_engine_HipRenderer_nBrushBox(void *, void *, jlong ctx, jint ox, jint oy, jint oz, jint w, jint h, jint d, jint value,
+                                           jint world_size, jint max_lod, jlong cb_addr) {
+  const int org[3] = {ox, oy, oz};
+  return svo_brush_box((svo_ctx *)(intptr_t)ctx, org, w, h, d, value, world_size, max_lod, (int32_t *)(intptr_t)cb_addr);
+}
+jlong Java_src_engine_HipRenderer_nBrushInfo(void *, void *, jlong ctx, jlong counts_addr, jlong ms_addr) {
+  uint64_t strokes = 0, v[4] = {0, 0, 0, 0};
+  const int rc = svo_brush_info((svo_ctx *)(intptr_t)ctx, &strokes, &v[0], &v[1], &v[2], &v[3], (float *)(intptr_t)ms_addr);
+  if (rc != SVO_OK) return (jlong)rc;
+  if (counts_addr) for (int i = 0; i < 4; i++) ((jlong *)(intptr_t)counts_addr)[i] = (jlong)v[i];
+  return (jlong)strokes;
+}
 jint Java_src_engine_HipRenderer_nSetCamera(void *, void *, jlong ctx, jfloat px, jfloat py, jfloat pz, jfloat l1x,
                                             jfloat l1y, jfloat l1z, jfloat l2x, jfloat l2y, jfloat l2z, jfloat r1x,
                                             jfloat r1y, jfloat r1z, jfloat r2x, jfloat r2y, jfloat r2z) {
@@ -189,6 +210,16 @@ jint Java_src_engine_HipRenderer_nGroupPoolUpload(void *, void *, jlong g, jlong
 }
 jint Java_src_engine_HipRenderer_nGroupPoolUpdate(void *, void *, jlong g, jlong base_addr, jlong start, jlong end) {
   return (start < 0 || end < 0) ? SVO_E_INVALID : svo_group_pool_update(GRP(g), (const void *)(intptr_t)base_addr, (uint64_t)start, (uint64_t)end);
+}
+jint Java_src_engine_HipRenderer_nGroupBrushSphere(void *, void *, jlong g, jint ox, jint oy, jint oz, jint radius, jint value,
+                                                   jint world_size, jint max_lod, jlong cb_addr) {
+  const int org[3] = {ox, oy, oz};
+  return svo_group_brush_sphere(GRP(g), org, radius, value, world_size, max_lod, (int32_t *)(intptr_t)cb_addr);
+}
+jint Java_src_engine_HipRenderer_nGroupBrushBox(void *, void *, jlong g, jint ox, jint oy, jint oz, jint w, jint h, jint d, jint value,
+                                                jint world_size, jint max_lod, jlong cb_addr) {
+  const int org[3] = {ox, oy, oz};
+  return svo_group_brush_box(GRP(g), org, w, h, d, value, world_size, max_lod, (int32_t *)(intptr_t)cb_addr);
 }
 jint Java_src_engine_HipRenderer_nGroupSetCamera(void *, void *, jlong g, jlong cam15_addr) {
   const float *c = (const float *)(intptr_t)cam15_addr;

@@ -23,6 +23,7 @@ EXPORTS = [
     "svo_set_reserved_cus", "svo_pool_commit", "svo_ring_forward_slot", "svo_dev_alloc", "svo_dev_free", "svo_dev_read",
     "svo_ipc_export", "svo_ipc_open", "svo_ipc_close", "svo_set_sequence", "svo_ring_submit_cams",
     "svo_build_from_heightmap16", "svo_launch_info",
+    "svo_pool_download_range", "svo_brush_sphere", "svo_brush_box", "svo_brush_info", "svo_group_brush_sphere", "svo_group_brush_box",
     "svo_group_create", "svo_group_destroy", "svo_group_last_error", "svo_group_size", "svo_group_member", "svo_group_pool_upload",
     "svo_group_pool_update", "svo_group_pool_download", "svo_group_build_from_heightmap", "svo_group_set_camera",
     "svo_group_set_params", "svo_group_set_pipeline", "svo_group_set_tuning", "svo_group_set_progressive", "svo_group_set_sequence",
@@ -71,6 +72,12 @@ def lib(path=None):
         L.svo_pool_upload.argtypes = [vp, vp, u64]
         L.svo_pool_update.argtypes = [vp, vp, u64, u64]
         L.svo_pool_download.argtypes = [vp, vp, u64]
+        L.svo_pool_download_range.argtypes = [vp, vp, u64, u64]
+        L.svo_brush_sphere.argtypes = [vp, vp] + [ci] * 4 + [vp]
+        L.svo_brush_box.argtypes = [vp, vp] + [ci] * 6 + [vp]
+        L.svo_brush_info.argtypes = [vp] + [ctypes.POINTER(u64)] * 5 + [fp]
+        L.svo_group_brush_sphere.argtypes = [vp, vp] + [ci] * 4 + [vp]
+        L.svo_group_brush_box.argtypes = [vp, vp] + [ci] * 6 + [vp]
         L.svo_pool_reserve.argtypes = [vp, u64]
         L.svo_pool_upload_device.argtypes = [vp, vp, u64]
         L.svo_build_from_heightmap.argtypes = [vp, vp, vp, ci, ctypes.POINTER(u64)]
@@ -227,6 +234,21 @@ class HipGroup:
         self._chk(self._L.svo_group_pool_download(self._h, out.ctypes.data, out.size))
         return out
 
+    def brush_sphere(self, origin, radius, value, world_size=0, max_lod=0):
+        """svo_group_brush_sphere: the stroke on every member's replica; returns [start0, end0, start1, end1]"""
+        org = np.asarray(origin, dtype=np.int32).reshape(3).copy()
+        cb = np.zeros(4, dtype=np.int32)
+        self._chk(self._L.svo_group_brush_sphere(self._h, org.ctypes.data, int(radius), int(value), int(world_size), int(max_lod),
+                                                 cb.ctypes.data))
+        return [int(v) for v in cb]
+
+    def brush_box(self, origin, w, h, d, value, world_size=0, max_lod=0):
+        org = np.asarray(origin, dtype=np.int32).reshape(3).copy()
+        cb = np.zeros(4, dtype=np.int32)
+        self._chk(self._L.svo_group_brush_box(self._h, org.ctypes.data, int(w), int(h), int(d), int(value), int(world_size),
+                                              int(max_lod), cb.ctypes.data))
+        return [int(v) for v in cb]
+
     def build_from_heightmap(self, height, material):
         height = np.ascontiguousarray(height, dtype=np.uint16)
         material = np.ascontiguousarray(material, dtype=np.uint8)
@@ -343,6 +365,37 @@ class HipContext:
         out = np.zeros(int(nbytes), dtype=np.uint8)
         self._chk(self._L.svo_pool_download(self._h, out.ctypes.data, out.size))
         return out
+
+    def pool_download_range(self, pool, start, end):
+        """svo_pool_download_range: bytes [start, end) of the device pool into the host copy `pool` (a writable uint8 array
+        that covers them), in place"""
+        assert pool.dtype == np.uint8 and pool.flags.c_contiguous and pool.flags.writeable and pool.size >= int(end)
+        self._chk(self._L.svo_pool_download_range(self._h, pool.ctypes.data, int(start), int(end)))
+
+    def brush_sphere(self, origin, radius, value, world_size=0, max_lod=0):
+        """svo_brush_sphere: Octree.useSDFBrush(new Sphere(origin, radius), value) on the device pool; returns the reference's
+        ChangeBounds [start0, end0, start1, end1] (end1 = the pool's new length).  world_size 0 = 8196, max_lod 0 = 13."""
+        org = np.asarray(origin, dtype=np.int32).reshape(3).copy()
+        cb = np.zeros(4, dtype=np.int32)
+        self._chk(self._L.svo_brush_sphere(self._h, org.ctypes.data, int(radius), int(value), int(world_size), int(max_lod), cb.ctypes.data))
+        return [int(v) for v in cb]
+
+    def brush_box(self, origin, w, h, d, value, world_size=0, max_lod=0):
+        """svo_brush_box: the same with new Box(origin, w, h, d)"""
+        org = np.asarray(origin, dtype=np.int32).reshape(3).copy()
+        cb = np.zeros(4, dtype=np.int32)
+        self._chk(self._L.svo_brush_box(self._h, org.ctypes.data, int(w), int(h), int(d), int(value), int(world_size), int(max_lod),
+                                        cb.ctypes.data))
+        return [int(v) for v in cb]
+
+    def brush_info(self):
+        """what the strokes did (svo_brush_info): strokes so far; of the last one the nodes visited and subdivided, the bytes
+        [lo, hi) it wrote below start1, its GPU time"""
+        v = [ctypes.c_uint64() for _ in range(5)]
+        ms = ctypes.c_float()
+        self._chk(self._L.svo_brush_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(ms)))
+        return {"strokes": int(v[0].value), "visited": int(v[1].value), "subdivided": int(v[2].value), "lo": int(v[3].value),
+                "hi": int(v[4].value), "gpu_ms": float(ms.value)}
 
     def pool_upload_device(self, dptr, nbytes):
         self._chk(self._L.svo_pool_upload_device(self._h, ctypes.c_void_p(int(dptr)), int(nbytes)))

@@ -297,6 +297,15 @@ class Renderer {
     check(svo_pool_update(ctx, data, (uint64_t)start, (uint64_t)end));
   }
   void getSSBO(uint8_t *out, size_t nbytes) { if (ensure()) check(svo_pool_download(ctx, out, nbytes)); }  // :148-150
+  // Octree.useSDFBrush + the two updateSSBO calls of Main.placeSDF (Main.java:338-353) on the device pool (svo_brush_*):
+  // cb = ChangeBounds {start0, end0, start1, end1}, may be null; worldSize 0 = Constants::WORLD_SIZE, maxLOD 0 = 13
+  void brushSphere(const int origin[3], int radius, int value, int32_t *cb = nullptr, int worldSize = 0, int maxLOD = 0) {
+    if (ensure()) check(svo_brush_sphere(ctx, origin, radius, value, worldSize, maxLOD, cb));
+  }
+  void brushBox(const int origin[3], int w, int h, int d, int value, int32_t *cb = nullptr, int worldSize = 0, int maxLOD = 0) {
+    if (ensure()) check(svo_brush_box(ctx, origin, w, h, d, value, worldSize, maxLOD, cb));
+  }
+  void getSSBO(uint8_t *base, uint64_t start, uint64_t end) { if (ensure() && start < end) check(svo_pool_download_range(ctx, base, start, end)); }
   Shader *getShaderByName(const std::string &name) {   // :152-158
     for (auto &s : shaders) if (s.name == name) return &s;
     return nullptr;

@@ -324,7 +324,14 @@ int svo_set_reserved_cus(svo_ctx *ctx, int per_xcd);
 int svo_ring_destroy(svo_ctx *ctx);
 /* enqueue frames frame_number .. frame_number + nframes - 1 (what nframes turns of Main.updateEarly with a static
  * camera render, Main.java:275) with the context's current camera / params / stripes / tuning into the next slot
- * (round robin; a slot's re-use is ordered behind its previous frames by its stream); returns at once. */
+ * (round robin; a slot's re-use is ordered behind its previous frames by its stream); returns at once.
+ * In render mode 0 the frames of such a submission differ in frameNumber only, and frameNumber first enters a path behind the
+ * primary cast (the pixel's random number in scatter()): on the persistent pipeline with the descriptor walk the primary ray
+ * of a pixel is cast ONCE per submission and every frame's bounce rays start from that one hit (persist_span_kernel; not with
+ * the beam pre-pass, several samples per pixel, sequences, paths of the primary ray alone (bounces 1), or the record walk).  Every frame's bytes are those of a
+ * dispatch of its own.  A submission of n frames with P primary and B bounce casts per frame therefore performs P + n B casts,
+ * not n (P + B); a ray rate formed from per-frame ray counts (bench.py) counts the casts the frames are bit-identical to, not
+ * the casts performed.  svo_ring_submit_cams is the like-for-like rate: every frame casts its own primaries there. */
 int svo_ring_submit(svo_ctx *ctx, int frame_number, int nframes, int *slot);
 /* the same for a camera that moves: frame k of the submission carries its own camera -- cams[15 k .. 15 k + 14] = pos, l1,
  * l2, r1, r2 as Camera.getUniform yields them (Camera.java:142-151) -- and its own frameNumber (Main.updateEarly moves the

@@ -16,7 +16,7 @@
 // the counting pass of svo_count_frame), the beam pass, the builder, the ring, the group.
 // SVO_VARIANTS=1 (libsvohip_variants.so, `make variants`; loaded by the tests that compare against them, like cxxloop): the same
 // plus the comparators -- pipeline 2 (staged wavefront tracing), the spare-ray kernel of round 5 (SVO_SPARE=1) -- and the
-// environment switches of the A/B runs (SVO_DERIVED, SVO_RC_TABLE, SVO_NORMAL_TABLE, SVO_FORCE_CAMS, SVO_PERSIST_*, ...).
+// environment switches of the A/B runs (SVO_DERIVED, SVO_RC_TABLE, SVO_NORMAL_TABLE, SVO_BATCH_PRIMARY, SVO_FORCE_CAMS, SVO_PERSIST_*, ...).
 #ifndef SVO_VARIANTS
 #define SVO_VARIANTS 0
 #endif

@@ -74,6 +74,9 @@ struct PersistArgs {
   const float *rc;
   uint32_t rc_stride;
   const float4 *ntab;   // unit normals by 16-bit code (svo_trav2.h), or null
+  // 1 = a band slot is a pixel with all the frames of the batch (persist_span_kernel): chosen once, in persist_launch
+  int span;
+  uint4 *prim;          // ... and the primary-hit records of its lanes, kSpanWords words per persistent lane of the launch
 };
 
 // n / d by multiply-high with m = ceil(2^32 / d) = (2^32 + e) / d, 0 <= e < d (made on the host, udiv_magic): with
@@ -269,9 +272,18 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 // horizontal fraction (of the column); of the pixel's random number (:26-29, :486) the two inner sin / fract chains (one a
 // function of the column and frameNumber, one of the row and frameNumber).  What stays in the round: three mixes, the
 // normalisation, the outer chain -- the same operations on the same values, so the same bits.
-template <int kMode, class Walk, bool kCams = false, bool kTab = false>
-__global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(const PersistArgs a) {
-  __shared__ typename Walk::Stack stk;
+// kSpan (persist_span_kernel; mode 0, one camera, one sample per pixel, f.batch > 1, f.bounces >= 2, no beam): a band slot is a
+// PIXEL, not a (frame, pixel) pair.  The frames of such a batch differ in frameNumber only, and frameNumber first enters a path in
+// scatter(), behind the primary cast (the pixel's random number): the primary ray of a pixel is the same ray in every frame of the
+// batch.  The lane casts it once, keeps what the shading of a primary hit reads (direction, voxel position, normal, value, t:
+// kSpanWords words) in a record of its own in global memory (a.prim: written once per pixel, read once per further frame;
+// registers would cost the kernel its sixth wave per SIMD), and runs frame 0's path, frame 1's, ... from that hit, each with its
+// own random number -- the same operations on the same values in the same order as the (frame, pixel) slots, so the same bytes.
+constexpr uint32_t kSpanWords = 12;   // three uint4 per persistent lane, [wave][3][lane]
+constexpr uint32_t kSpanSun = 1u << 16;   // in a kSpan lane's `seg`: a miss of the segment under way adds the sun's light
+template <int kMode, class Walk, bool kCams, bool kTab, bool kSpan>
+__device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk::Stack &stk) {
+  static_assert(!kSpan || (kMode == 0 && !kCams), "a batch shares its primary ray only in mode 0 with one camera");
   const uint32_t lane = threadIdx.x;
   const Frame &f = a.f;
   Walk walk;
@@ -282,8 +294,8 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
   typename Walk::State t;
   int status = ST_IDLE;
   uint32_t pix = 0, seg = 0;   // seg: path segment in the low byte; a.fold > 1: sample index in bits 8..23, frame of the batch above
-  int px = 0, py = 0;
-  // path state that outlives a cast
+                               // (kSpan: the frame the lane's pixel has reached, in the same place)
+  int px = 0, py = 0;  // path state that outlives a cast
   V3 d = mk(0.f, 0.f, 0.f), mask = mk(1.f, 1.f, 1.f), accum = mk(0.f, 0.f, 0.f), normal = mk(0.f, 0.f, 0.f);
   float r = 0.0f, depth = 0.0f;
   uint32_t value = 0;
@@ -313,7 +325,7 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
     st_lanes_shaded += (unsigned long long)__builtin_popcountll(__ballot(status >= ST_HIT));
 #endif
     if (status >= ST_HIT) {
-      const Cast c = walk.result(t, status);
+      Cast c = walk.result(t, status);
 #ifdef SVO_STAMPS
       asm volatile("" ::"v"(c.t), "v"(c.pointer), "v"(c.normal.x), "v"(c.voxel_pos.x), "v"(c.value) : "memory");   // the record is here
       st_r1 = __builtin_readcyclecounter();
@@ -328,9 +340,94 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
         h.w = c.hit ? __float_as_uint(c.t) : 0u;
         if (kMode == 4) h = make_uint4(0u, 0u, 0u, 0u);   // trace() casts nothing in modes >= 4 (svotrace.comp:643-646)
         a.hits[pix] = h;
+        if (kSpan)   // the one primary cast is every frame's: the same record into every frame's plane
+          for (int k = 1; k < f.batch; k++) a.hits[pix + (uint32_t)k * f.frame_stride] = h;
       }
       emit = true;
-      if (kMode == 0) {
+      if constexpr (kSpan) {
+        // One shading per stopped lane and round, whatever the lane does next.  A cast that ends its frame's path -- a bounce that
+        // left the octree, or the hit of the last segment -- needs no scatter() of its own here: what a miss adds was decided when
+        // the ray was set up (kSpanSun, below), and a last hit emits the sums as they stand.  So the lane emits, takes its
+        // pixel's next frame (the primary hit from its record, that frame's random number) and shades THAT in the same pass as the
+        // lanes whose primary or inner segment just hit.  (persist_launch: f.bounces >= 2, so a shaded hit always goes on.)
+        // (the address is formed here, in the round: hoisted in front of the kernel's loop it is two registers spilled for good)
+        uint32_t rl = lane;
+        asm volatile("" : "+v"(rl));
+        uint4 *const rec = a.prim + (size_t)blockIdx.x * (64u * kSpanWords / 4u) + rl;   // [3][64] uint4 per wave
+        const V3 sun = normalize3(mk(1.0f, 1.0f, 1.0f));
+        bool shade = true;
+        if (segn == 0u) {
+          if (c.hit) {   // the pixel's primary hit, for all its frames
+            rec[0] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(c.t));
+            rec[64] = make_uint4(__float_as_uint(c.voxel_pos.x), __float_as_uint(c.voxel_pos.y), __float_as_uint(c.voxel_pos.z), c.value);
+            rec[128] = make_uint4(__float_as_uint(c.normal.x), __float_as_uint(c.normal.y), __float_as_uint(c.normal.z), 0u);
+            emit = false;
+          } else {
+            const V3 s = sky_colour(d);
+            ecol = mk(0.0f + s.x, 0.0f + s.y, 0.0f + s.z);
+            shade = false;
+          }
+        } else if (!c.hit || (int)segn + 1 >= f.bounces) {   // frame (seg >> 24)'s path ends
+          if (c.hit) {
+            accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
+            edepth = c.t;
+          } else {
+            if ((seg & kSpanSun) != 0u) accum = mk(accum.x + mask.x * 7.0f, accum.y + mask.y * 7.0f, accum.z + mask.z * 7.0f);
+            accum = mk(accum.x + mask.x * 1.0f, accum.y + mask.y * 1.0f, accum.z + mask.z * 1.0f);
+          }
+          // (stored here, not behind the block with the other lanes' pixels: the colour would stay live across the shading below,
+          // four registers the kernel does not have)
+          persist_emit(a, pix, 0u, px, py, accum, edepth);
+          emit = false;
+          const uint32_t fi = (seg >> 24) + 1u;
+          shade = fi < (uint32_t)f.batch;
+          if (shade) {   // the pixel's next frame: a refilled lane's path state, the primary hit as it was
+            const uint4 r0 = rec[0], r1 = rec[64], r2 = rec[128];
+            d = mk(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
+            c.t = __uint_as_float(r0.w);
+            c.voxel_pos = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
+            c.value = r1.w;
+            c.normal = mk(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z));
+            seg = fi << 24;
+            pix += f.frame_stride;
+            mask = mk(1.f, 1.f, 1.f);
+            accum = mk(0.f, 0.f, 0.f);
+            if (kTab) {
+              const float *fr = a.rc + (size_t)fi * a.rc_stride;
+              const float colx = fr[2 * px], roww = fr[((2 * f.width + 3) & ~3) + 8 * py + 3];
+              r = rand_of_dot(((float)px + colx) * 12.9898f + ((float)py + roww) * 78.233f);
+            } else {
+              r = pixel_rand((float)px, (float)py, (float)(f.frame_number + (int)fi + a.sample));
+            }
+          }
+        } else {
+          emit = false;   // an inner segment's hit
+        }
+        if (shade) {   // a hit the path goes on from: the same operations as below
+          normal = c.normal; value = c.value;
+          const V3 vpos = c.voxel_pos;
+          const bool mirror = ((f.mirror_mask >> (value & 31u)) & 1u) != 0u;
+          const V3 nd = scatter(d, normal, r, mirror);
+          const V3 mc = material_colour(value, mk(vpos.x - 1.0f, vpos.y - 1.0f, vpos.z - 1.0f));
+          depth = c.t;
+          accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
+          mask = mk(mask.x * mc.x, mask.y * mc.y, mask.z * mc.z);
+          const float k = dot3(nd, normal);
+          mask = mk(mask.x * k, mask.y * k, mask.z * k);
+          d = nd;
+          seg++;
+          ninit = true; icone = true; io = vpos;
+          status = ST_ACTIVE;
+          // kSpanSun: should the new ray leave the octree, the path ends with scatter(d, normal, r) of exactly these values (a
+          // miss changes neither normal nor value) against the sun: one bit, taken now, while the lane shades anyway.  Every
+          // shaded hit pays for this second scatter(), the hit of an inner segment too, whether or not its next ray misses:
+          // per path that is the scatter() the (frame, pixel) kernel runs when the path ends, moved here.  The bit equals that
+          // kernel's only because both inlined copies of scatter() are the same IEEE operations (-ffp-contract=off, no
+          // fast-math); tests/test_gpu_batch_primary.py holds the bytes against it and against the oracle.
+          const V3 nd2 = scatter(d, normal, r, mirror);
+          seg = acos_pinned(dot3(nd2, sun)) < 0.4f ? (seg | kSpanSun) : (seg & ~kSpanSun);
+        }
+      } else if (kMode == 0) {
         if (segn == 0u && !c.hit) {
           const V3 s = sky_colour(d);
           ecol = mk(0.0f + s.x, 0.0f + s.y, 0.0f + s.z);
@@ -412,7 +509,14 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
       if (m != 0) { st_part[0] += m - st_t0; st_part[1] += st_r2 - m; }
     }
 #endif
-    if (emit) persist_emit(a, pix, seg >> 8, px, py, ecol, edepth);
+    if (emit) {
+      if (kSpan) {
+        // (only primary misses come here: the same sky in every frame of the batch)
+        for (int k = 0; k < f.batch; k++) persist_emit(a, pix + (uint32_t)k * f.frame_stride, 0u, px, py, ecol, edepth);
+      } else {
+        persist_emit(a, pix, seg >> 8, px, py, ecol, edepth);
+      }
+    }
 
 #ifdef SVO_STAMPS
     { const unsigned long long now = __builtin_readcyclecounter(); st_shade += now - st_t0; st_part[2] += now - st_r2; st_r2 = now; }
@@ -434,7 +538,8 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
         int band_rows = f.tiles_y - first_row;
         band_rows = band_rows < 0 ? 0 : (band_rows > a.rows_per_band ? a.rows_per_band : band_rows);
         const uint32_t band_frame = (uint32_t)(band_rows * f.tiles_x) * 64u;   // pixel slots of the band in one frame
-        const uint32_t band_total = band_frame * (uint32_t)(f.batch * a.fold);   // ... and over the launch's frames x samples
+        // ... and over the launch's frames x samples (kSpan: a slot is a pixel, with all its frames)
+        const uint32_t band_total = kSpan ? band_frame : band_frame * (uint32_t)(f.batch * a.fold);
 #else
         const int first_tile = (int)band * a.tiles_per_band;
         int band_tiles = f.ntiles - first_tile;
@@ -458,7 +563,7 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
           const uint32_t per_frame = band_frame * (uint32_t)a.fold;
           const uint32_t tiles_pf = per_frame >> 6;   // tile slots of the band per frame
           const int full_band = band_rows == a.rows_per_band ? 0 : 1;
-          const uint32_t fi = f.batch > 1 ? udiv_by(slot >> 6, tiles_pf, a.mg_tpf[full_band]) : 0u;
+          const uint32_t fi = !kSpan && f.batch > 1 ? udiv_by(slot >> 6, tiles_pf, a.mg_tpf[full_band]) : 0u;
           const uint32_t q = (slot - fi * per_frame) >> 6;
           uint32_t si = 0u;
           int j = (int)q;
@@ -615,6 +720,19 @@ __global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(con
 #endif
 }
 
+template <int kMode, class Walk, bool kCams = false, bool kTab = false>
+__global__ __launch_bounds__(64, WalkWaves<Walk>::value) void persist_kernel(const PersistArgs a) {
+  __shared__ typename Walk::Stack stk;
+  persist_body<kMode, Walk, kCams, kTab, false>(a, stk);
+}
+
+// a static-camera batch of mode 0 on the descriptor walk: one primary cast per pixel for all the frames of the batch (kSpan)
+template <bool kTab>
+__global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_span_kernel(const PersistArgs a) {
+  __shared__ DescWalk::Stack stk;
+  persist_body<0, DescWalk, false, kTab, true>(a, stk);
+}
+
 // a.fold > 1: tiles per group of a band's walk.  1 / 8 / 64 / 512 / all: 4.47 / 4.49 / 4.47 / 4.41 / 4.20 Grays/s at 64
 // samples per pixel (tools/history/r03_fold2.sh): a group's samples should be in flight together, not a whole band's
 constexpr int kFoldGroup = 8;
@@ -653,6 +771,10 @@ struct PersistBuffers {
   size_t rc_floats[8] = {};
   uint32_t *prec[8] = {};      // path records of the spare-ray kernel, one buffer per counter set
   size_t prec_words = 0;
+  int span_mode = 1;   // 1 = a static-camera batch of mode 0 casts its primary rays once (persist_span_kernel); environment
+                       // SVO_BATCH_PRIMARY=0: every frame of the batch casts its own
+  uint4 *prim[8] = {};         // primary-hit records of persist_span_kernel's lanes, one buffer per counter set
+  size_t prim_waves = 0;       // persistent waves each of them has room for
   int last_thresh = 9;
   int waves_per_cu = 0;      // 0 = automatic: as many as fit (occupancy query) for one launch at a time, kRingWavesPerCu for
                              // the submissions of a ring with more than one slot (in_ring, set around the launch by ring_submit)
@@ -670,14 +792,15 @@ inline void persist_free(PersistBuffers &b) {
   if (b.heads) (void)hipFree(b.heads);
   for (auto &p : b.prec) if (p) (void)hipFree(p);
   for (auto &p : b.rc) if (p) (void)hipFree(p);
+  for (auto &p : b.prim) if (p) (void)hipFree(p);
   for (auto &f : b.facc) if (f) (void)hipFree(f);
   for (auto &e : b.head_done) if (e) (void)hipEventDestroy(e);
   for (auto &e : b.facc_done) if (e) (void)hipEventDestroy(e);
   const int wpc = b.waves_per_cu, th = b.thresh_num, sm = b.spare_mode, tm = b.table_mode;   // tuning survives a resize
   const float4 *nt = b.ntab;
-  const int nm = b.ntab_mode;
+  const int nm = b.ntab_mode, sp = b.span_mode;
   b = PersistBuffers();
-  b.waves_per_cu = wpc; b.thresh_num = th; b.spare_mode = sm; b.table_mode = tm; b.ntab = nt; b.ntab_mode = nm;
+  b.waves_per_cu = wpc; b.thresh_num = th; b.spare_mode = sm; b.table_mode = tm; b.ntab = nt; b.ntab_mode = nm; b.span_mode = sp;
 }
 
 // The row / column tables of a launch: per frame of the batch W + H threads.  A handful of workgroups: unlike a kernel of one
@@ -756,6 +879,11 @@ inline void persist_launch_mode(const PersistArgs &a, int blocks, hipStream_t st
 #if SVO_HAVE_SPARE
   if (a.spare) { persist2_launch_mode<kMode>(a, blocks, stream); return; }
 #endif
+  if (kMode == 0 && a.span) {   // (persist_launch: mode 0, one camera, the descriptor walk; any other mode runs its own kernel)
+    if (a.rc) hipLaunchKernelGGL((persist_span_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((persist_span_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+    return;
+  }
   if (a.rc && a.desc) {   // (the tables are only made for launches that walk the descriptor table)
     if (a.fvar) hipLaunchKernelGGL((persist_kernel<kMode, DescWalk, true, true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((persist_kernel<kMode, DescWalk, false, true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
@@ -858,6 +986,7 @@ inline int persist_launch(PersistBuffers &b, const uint8_t *pool, const Frame &f
     if (const char *e3 = getenv("SVO_SPARE")) b.spare_mode = atoi(e3) != 0 ? 1 : 0;
     if (const char *e4 = getenv("SVO_RC_TABLE")) b.table_mode = atoi(e4) != 0 ? 1 : 0;
     if (const char *e5 = getenv("SVO_NORMAL_TABLE")) b.ntab_mode = atoi(e5) != 0 ? 1 : 0;
+    if (const char *e6 = getenv("SVO_BATCH_PRIMARY")) b.span_mode = atoi(e6) != 0 ? 1 : 0;
 #endif
   }
   // the spare-ray kernel walks the descriptor table in assembly: pools the table cannot state, and builds with hipcc's
@@ -933,24 +1062,42 @@ inline int persist_launch(PersistBuffers &b, const uint8_t *pool, const Frame &f
   a.group = kFoldGroup;
   a.desc = desc; a.aux = aux; a.desc_count = desc_count;
   a.fvar = fvar;
+  // Consecutive frame numbers under one camera (the reference's still camera: frameNumber advances only while the camera stands,
+  // Main.java:225-233) share their primary rays in mode 0: one slot per pixel, the primary cast once for the whole batch.  Frames
+  // with their own cameras, several samples per pixel (folded or a launch each) / sequences, beam launches, paths of the primary
+  // ray alone (every frame of those is the same image), the record walk and the spare-ray kernel keep a slot per (frame, pixel).
+  const bool span = SVO_BAND_COLMAJOR && b.span_mode != 0 && f.render_mode == 0 && fvar == nullptr && fold == 1 && !resolve &&
+                    f.batch > 1 && f.bounces >= 2 && f.use_beam == 0 && desc != nullptr && !spare_kernel;
+  a.span = span ? 1 : 0;
+  const int slot_frames = span ? 1 : (f.batch > 1 ? f.batch : 1);   // frames a band's slots are counted over
   {
     const int last_rows = a.rows_per_band > 0 ? f.tiles_y % a.rows_per_band : 0;   // the one band that is not full (if any)
     const uint32_t tpf[2] = {(uint32_t)(a.rows_per_band * f.tiles_x * fold), (uint32_t)(last_rows * f.tiles_x * fold)};
-    const uint64_t nb = (uint64_t)(f.batch > 1 ? f.batch : 1);
+    const uint64_t nb = (uint64_t)slot_frames;
     a.mg_rows[0] = udiv_magic((uint32_t)a.rows_per_band, (uint64_t)a.rows_per_band * (uint64_t)f.tiles_x);
     a.mg_rows[1] = udiv_magic((uint32_t)last_rows, (uint64_t)last_rows * (uint64_t)f.tiles_x);
     a.mg_tpf[0] = udiv_magic(tpf[0], nb * tpf[0]);   // n = slot >> 6 < frames x tile slots per frame
     a.mg_tpf[1] = udiv_magic(tpf[1], nb * tpf[1]);
   }
-  const long long work = (long long)f.ntiles * (f.batch > 1 ? f.batch : 1) * fold;
+  const long long work = (long long)f.ntiles * slot_frames * fold;
   const int blocks = work < (long long)b.blocks ? (int)work : b.blocks;
   b.last_blocks = blocks;
+  if (span && b.prim_waves < (size_t)blocks) {   // grow all sets at once, for as many waves as a launch of this shape can have
+    const size_t waves = (size_t)std::max(b.blocks, blocks);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;   // (launches in flight may still use the old records)
+    for (auto &p : b.prim) { if (p) (void)hipFree(p); p = nullptr; }
+    b.prim_waves = 0;
+    for (auto &p : b.prim)
+      if ((e = hipMalloc((void **)&p, waves * 64 * kSpanWords * sizeof(uint32_t))) != hipSuccess) return (int)e;
+    b.prim_waves = waves;
+  }
   // a ring of counter sets: frames may be in flight on different streams at the same time.  A frame's sample launches
   // are ordered by its stream, so they share the frame's set; only another frame's re-use waits (for the event)
   const int hset = (int)(frame_no % kHeadSets);
   a.heads = b.heads + (size_t)hset * kHeadWords;
   a.prec = (spare_kernel && SVO_SPARE_RECORDS) ? b.prec[hset] : nullptr;   // (a counter set's launches are ordered by the set's event: so are its records)
   a.spare = spare_kernel ? 1 : 0;
+  a.prim = span ? b.prim[hset] : nullptr;   // (likewise)
   // the row / column tables: launches that carry one sample per pixel (samples / sequences folded into a launch seed every
   // sample of a pixel differently and keep computing in the round), on the descriptor walk, not the spare-ray kernel
   a.rc = nullptr; a.rc_stride = 0;

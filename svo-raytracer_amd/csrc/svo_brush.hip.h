@@ -157,18 +157,21 @@ __global__ __launch_bounds__(64) void march_kernel(Item *items, uint32_t lo, uin
   }
 }
 
-// The eight children of the record at `ptr` (forEachChild, Octree.java:901-923): false when one of them lies outside the pool
-__device__ inline bool children_of(const uint8_t *pool, uint32_t pool_len, uint32_t ptr, uint32_t cptr[8], uint32_t ctag[8]) {
-  const long long cp0 = (long long)ptr + (long long)be32(pool + ptr + 1);
-  const uint32_t mask = ((uint32_t)pool[ptr + 5] << 8) | (uint32_t)pool[ptr + 6];
-  long long cp = cp0;
+// The eight children of the record at `ptr` as the leaf mask `mask` lays them out (forEachChild, Octree.java:901-923): false
+// when one of them -- its whole record, or (!whole) its value byte -- lies outside the pool
+__device__ inline bool children_at(const uint8_t *pool, uint32_t pool_len, uint32_t ptr, uint32_t mask, bool whole, uint32_t cptr[8],
+                                   uint32_t ctag[8]) {
+  long long cp = (long long)ptr + (long long)be32(pool + ptr + 1);
   for (uint32_t c = 0; c < 8u; c++) {
     const uint32_t tag = (mask >> (2u * c)) & 3u, sz = rec_size(tag);
-    if (cp < 0 || cp + (long long)sz > (long long)pool_len) return false;
+    if (cp < 0 || cp + (long long)(whole ? sz : 1u) > (long long)pool_len) return false;
     cptr[c] = (uint32_t)cp; ctag[c] = tag;
     cp += sz;
   }
   return true;
+}
+__device__ inline bool children_of(const uint8_t *pool, uint32_t pool_len, uint32_t ptr, uint32_t cptr[8], uint32_t ctag[8]) {
+  return children_at(pool, pool_len, ptr, ((uint32_t)pool[ptr + 5] << 8) | (uint32_t)pool[ptr + 6], true, cptr, ctag);
 }
 
 // What happens to each item of [lo, lo + n) (the private useSDFBrush, Octree.java:710-827), and its children's items
@@ -310,17 +313,24 @@ __global__ __launch_bounds__(256) void write_kernel(uint8_t *pool, uint32_t star
     uint32_t cptr[8], ctag[8];
     // (decide_kernel has checked these bytes; checked again, so that a pool with shared subtrees, where another thread may
     // have rewritten them by now, still stays in bounds)
-    const bool inside = children_of(pool, start1, ptr, cptr, ctag);
+    bool inside;
+    if (i == 0u) {
+      // The root is its own parent, child number 0: the reference re-tags that child to a 7-byte leaf in the root's mask
+      // BEFORE it walks the root's children (Octree.java:797-808), so the walk lays them out by the patched mask -- where
+      // child 0 was a 3-byte or 1-byte record, the marks land behind the other children's value bytes.  Only value bytes
+      // are written, so only they have to lie below start1.
+      const uint32_t mask = (((((uint32_t)pool[5] << 8) | (uint32_t)pool[6]) & ~3u) | 2u);
+      inside = children_at(pool, start1, ptr, mask, false, cptr, ctag);
+      pool[5] = (uint8_t)(mask >> 8); pool[6] = (uint8_t)mask;
+      note_written(ctr, 5u, 7u);
+    } else {
+      inside = children_of(pool, start1, ptr, cptr, ctag);
+    }
     pool[ptr] = (uint8_t)value;
     note_written(ctr, ptr, ptr + 1u);
     for (uint32_t c = 0; inside && c < 8u; c++) {       // markNodeAsDirty
       pool[cptr[c]] = kDeleteValue;
       note_written(ctr, cptr[c], cptr[c] + 1u);
-    }
-    if (i == 0u) {   // the root is its own parent, child number 0
-      const uint32_t mask = (((((uint32_t)pool[5] << 8) | (uint32_t)pool[6]) & ~3u) | 2u);
-      pool[5] = (uint8_t)(mask >> 8); pool[6] = (uint8_t)mask;
-      note_written(ctr, 5u, 7u);
     }
   } else if (dec == kRecurse) {
     uint32_t mask = ((uint32_t)pool[ptr + 5] << 8) | (uint32_t)pool[ptr + 6];

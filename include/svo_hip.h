@@ -252,6 +252,32 @@ int svo_brush_box(svo_ctx *ctx, const int origin[3], int w, int h, int d, int va
  * [start1, end1), not cb's first range.  Any may be NULL. */
 int svo_brush_info(svo_ctx *ctx, uint64_t *strokes, uint64_t *visited, uint64_t *subdivided, uint64_t *lo, uint64_t *hi, float *gpu_ms);
 
+/* ---- compaction of the device pool ---------------------------------------------------- */
+/* No reference equivalent (Octree.getSubtreeRange is a stub): strokes only append, and a filled node's former subtree stays
+ * in the pool, unreachable.  Rewrites the context's pool as exactly its reachable records in the builder's order: the root
+ * record at offset 0 (always interior), a node's children block behind it, then the subtrees of the block's tag-0 children in
+ * child order.  Reachable goes by tag: an interior node of value 0 keeps its subtree, a tag-2 leaf's stale pointer is not
+ * followed.  Records are copied verbatim (leaves with all their bytes); only the relative child pointers of interior records
+ * are recomputed.  A pool that is already in that order comes back byte for byte: what the builders make up to 2048^3; above
+ * that they lay the levels over the 1024^3 chunks out first (Octree.fillEmptyChildren), and the pool comes back with the same
+ * length and every chunk behind the block that holds its node.  A children block that several interior
+ * records share is copied once per record, so the result may be larger than the input.
+ * *old_nbytes / *new_nbytes (may be NULL): the pool's length before and after.  Like every pool mutator the call waits for
+ * the whole device first (ring slots in flight, pending dispatches).  The plan is made before anything is written: when a
+ * reachable block starts or ends outside the pool, or the tree has more than 13 levels of block-owning nodes (the depth the
+ * ray walk supports; a cycle ends here) (SVO_E_INVALID), or the node lists would pass 2^27 nodes or the result 2^31 bytes
+ * (SVO_E_TOOLARGE), the pool, its length, the derived tables and the stroke counters are as they were.
+ * Device memory a call takes beside the pool, until it returns: the new pool (its length + 64 bytes) and 20 bytes per reachable
+ * block-owning node (builder output: about half the pool's size again; at most 2.5 GiB), plus 4 bytes per 1024 nodes of scan
+ * scratch.  The old buffer is freed on success.
+ * Afterwards every byte offset into the old pool is void (hit-record pointers, ChangeBounds, svo_brush_info's lo / hi), the
+ * descriptor table and the beam liveness table are rebuilt at the next dispatch as after svo_pool_upload, and the next stroke
+ * appends at the new end. */
+int svo_pool_compact(svo_ctx *ctx, uint64_t *old_nbytes, uint64_t *new_nbytes);
+/* what compaction did: *calls that succeeded so far, and of the last one the *records copied (the root included), the
+ * *levels of block-owning nodes and the GPU time of planning and writing.  Any may be NULL. */
+int svo_compact_info(svo_ctx *ctx, uint64_t *calls, uint64_t *records, int *levels, float *gpu_ms);
+
 /* record per-pixel svo_hit (costs 16 B/pixel of stores); default on */
 int svo_set_hit_records(svo_ctx *ctx, int enabled);
 
@@ -406,6 +432,9 @@ int svo_group_pool_download(svo_group *g, void *host, uint64_t nbytes);
 /* svo_brush_sphere / svo_brush_box on every member's replica of the pool (the same bytes and the same cb on each) */
 int svo_group_brush_sphere(svo_group *g, const int origin[3], int radius, int value, int world_size, int max_lod, int32_t cb[4]);
 int svo_group_brush_box(svo_group *g, const int origin[3], int w, int h, int d, int value, int world_size, int max_lod, int32_t cb[4]);
+/* svo_pool_compact on every member's replica; SVO_E_INVALID when a member's lengths differ from member 0's (the replicas
+ * were not equal).  A member's refusal leaves that member and the ones behind it as they were. */
+int svo_group_pool_compact(svo_group *g, uint64_t *old_nbytes, uint64_t *new_nbytes);
 int svo_group_build_from_heightmap(svo_group *g, const uint16_t *height, const uint8_t *material, int n, uint64_t *out_nbytes);
 int svo_group_set_camera(svo_group *g, const float pos[3], const float l1[3], const float l2[3], const float r1[3], const float r2[3]);
 int svo_group_set_params(svo_group *g, int frame_number, int render_mode, int buffer_end, int use_beam, int bounces,

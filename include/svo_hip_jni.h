@@ -44,6 +44,14 @@ jint Java_src_engine_HipRenderer_nBrushBox(void *env, void *cls, jlong ctx, jint
 /* svo_brush_info: returns the strokes made so far (or a negative status); counts_addr: 4 longs {visited, subdivided, lo,
  * hi} of the last one, ms_addr: 1 float (its GPU time); 0 = not wanted */
 jlong Java_src_engine_HipRenderer_nBrushInfo(void *env, void *cls, jlong ctx, jlong counts_addr, jlong ms_addr);
+/* svo_pool_compact: the device pool rewritten as its reachable records; sizes_addr: 2 longs {bytes before, bytes after},
+ * 0 = not wanted */
+jint Java_src_engine_HipRenderer_nPoolCompact(void *env, void *cls, jlong ctx, jlong sizes_addr);
+/* svo_compact_info: returns the calls made so far (or a negative status); counts_addr: 2 longs {records copied, levels} of
+ * the last one, ms_addr: 1 float (its GPU time); 0 = not wanted */
+jlong Java_src_engine_HipRenderer_nCompactInfo(void *env, void *cls, jlong ctx, jlong counts_addr, jlong ms_addr);
+/* svo_group_pool_compact: every member's replica */
+jint Java_src_engine_HipRenderer_nGroupPoolCompact(void *env, void *cls, jlong g, jlong sizes_addr);
 /* the stroke on every member's replica (svo_group_brush_*) */
 jint Java_src_engine_HipRenderer_nGroupBrushSphere(void *env, void *cls, jlong g, jint ox, jint oy, jint oz, jint radius, jint value,
                                                    jint world_size, jint max_lod, jlong cb_addr);

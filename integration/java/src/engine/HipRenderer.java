@@ -189,6 +189,28 @@ public class HipRenderer {
     return cb;
   }
 
+  /**
+   * svo_pool_compact: the device pool rewritten as exactly its reachable records, in the builder's order; returns {bytes
+   * before, bytes after}.  Every offset into the old pool is void afterwards (hit-record pointers, cached ChangeBounds), and
+   * a host copy of the pool has to be fetched again whole (getSSBO).
+   */
+  public long[] compactPool() {
+    ByteBuffer sizes = MemoryUtil.memAlloc(16);
+    check(nPoolCompact(ctx, MemoryUtil.memAddress(sizes)));
+    long[] out = {sizes.getLong(0), sizes.getLong(8)};
+    MemoryUtil.memFree(sizes);
+    return out;
+  }
+
+  /** svo_compact_info: {calls so far, records copied, levels} of the last compaction. */
+  public long[] compactInfo() {
+    ByteBuffer counts = MemoryUtil.memAlloc(16);
+    long calls = nCompactInfo(ctx, MemoryUtil.memAddress(counts), 0L);
+    long[] out = {calls, counts.getLong(0), counts.getLong(8)};
+    MemoryUtil.memFree(counts);
+    return out;
+  }
+
   public Shader getShaderByName(String name) {
     for (Shader shader : shaders) {
       if (shader.name.equals(name))
@@ -568,6 +590,15 @@ public class HipRenderer {
       return out;
     }
 
+    /** HipRenderer.compactPool on every GPU's replica of the pool: {bytes before, bytes after}, the same on all of them. */
+    public long[] compactPool() {
+      ByteBuffer sizes = MemoryUtil.memAlloc(16);
+      check(nGroupPoolCompact(g, MemoryUtil.memAddress(sizes)));
+      long[] out = {sizes.getLong(0), sizes.getLong(8)};
+      MemoryUtil.memFree(sizes);
+      return out;
+    }
+
     /** Main.placeSDF (Main.java:338-353) with the stroke made on every GPU. */
     public int[] placeSDF(int ox, int oy, int oz, int radius, int value) {
       long t0 = System.currentTimeMillis();
@@ -694,6 +725,9 @@ public class HipRenderer {
   private static native int nBrushBox(long ctx, int ox, int oy, int oz, int w, int h, int d, int value, int worldSize,
       int maxLOD, long cbAddr);
   private static native long nBrushInfo(long ctx, long countsAddr, long msAddr);
+  private static native int nPoolCompact(long ctx, long sizesAddr);
+  private static native long nCompactInfo(long ctx, long countsAddr, long msAddr);
+  private static native int nGroupPoolCompact(long g, long sizesAddr);
   private static native int nSetCamera(long ctx, float px, float py, float pz, float l1x, float l1y, float l1z,
       float l2x, float l2y, float l2z, float r1x, float r1y, float r1z, float r2x, float r2y, float r2z);
   private static native int nSetParams(long ctx, int frameNumber, int renderMode, int bufferEnd, int useBeam,

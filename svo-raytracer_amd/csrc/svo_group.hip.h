@@ -221,6 +221,23 @@ int svo_group_brush_box(svo_group *g, const int origin[3], int w, int h, int d, 
   if (!g) return SVO_E_INVALID;
   GALL(g, svo_brush_box(c, origin, w, h, d, value, world_size, max_lod, cb));
 }
+// every member compacts its own replica: the same bytes in, the same bytes out
+int svo_group_pool_compact(svo_group *g, uint64_t *old_nbytes, uint64_t *new_nbytes) {
+  if (!g) return SVO_E_INVALID;
+  uint64_t o0 = 0, n0 = 0;
+  for (int r = 0; r < g->n; r++) {
+    uint64_t o = 0, n = 0;
+    const int rc = gmember(g, r, svo_pool_compact(g->m[(size_t)r], &o, &n));
+    if (rc) return rc;
+    if (r == 0) { o0 = o; n0 = n; }
+    else if (o != o0 || n != n0)
+      return gfail(g, SVO_E_INVALID, "svo_group_pool_compact: member " + std::to_string(r) + "'s pool went from " + std::to_string(o) + " to " +
+                                         std::to_string(n) + " bytes, member 0's from " + std::to_string(o0) + " to " + std::to_string(n0));
+  }
+  if (old_nbytes) *old_nbytes = o0;
+  if (new_nbytes) *new_nbytes = n0;
+  return SVO_OK;
+}
 int svo_group_build_from_heightmap(svo_group *g, const uint16_t *height, const uint8_t *material, int n, uint64_t *out_nbytes) {
   if (!g) return SVO_E_INVALID;
   int rc = gmember(g, 0, svo_build_from_heightmap(g->m[0], height, material, n, out_nbytes));

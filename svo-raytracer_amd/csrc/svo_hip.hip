@@ -32,6 +32,7 @@
 #include "svo_beam.hip.h"
 #include "svo_derive.hip.h"
 #include "svo_brush.hip.h"
+#include "svo_compact.hip.h"
 
 using namespace svo;
 
@@ -116,6 +117,7 @@ struct svo_ctx {
 #endif
   PersistBuffers pb;
   brush::State bs;             // work items and counters of svo_brush_* (made at the first stroke), what the last stroke did
+  compact::State cs;           // events of svo_pool_compact (made at the first call), what the last call did
   // frames in flight behind the boundary (svo_ring_*): per slot a stream of its own, output buffers for up to
   // ring_frames consecutive frames, and the events around its last submission
   struct RingSlot : Planes {        // (the planes: library-owned images, frame after frame)
@@ -291,6 +293,7 @@ int svo_destroy(svo_ctx *c) {
   if (c->d_beam_live) (void)hipFree(c->d_beam_live);
   derive::free_table(c->dt);
   brush::free_state(c->bs);
+  compact::free_state(c->cs);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   ring_free(c);
@@ -551,6 +554,50 @@ int svo_brush_info(svo_ctx *c, uint64_t *strokes, uint64_t *visited, uint64_t *s
   if (lo) *lo = c->bs.lo;
   if (hi) *hi = c->bs.hi;
   if (gpu_ms) *gpu_ms = c->bs.gpu_ms;
+  return SVO_OK;
+}
+
+// ---------------------------------------------------------------- compaction (svo_compact.hip.h)
+int svo_pool_compact(svo_ctx *c, uint64_t *old_nbytes, uint64_t *new_nbytes) {
+  if (!c) return SVO_E_INVALID;
+  if (!c->d_pool || c->pool_len < 7) return fail(c, SVO_E_NOPOOL, "svo_pool_compact: no pool uploaded");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());   // see svo_pool_upload
+  hipStream_t st = c->sets[0].stream;
+  compact::State &s = c->cs;
+  if (!s.e0) HIPCHK(c, hipEventCreate(&s.e0));
+  if (!s.e1) HIPCHK(c, hipEventCreate(&s.e1));
+  HIPCHK(c, hipEventRecord(s.e0, st));
+  compact::Result r;
+  hipError_t e = compact::run(c->d_pool, (uint32_t)c->pool_len, kPad, st, r);
+  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("svo_pool_compact: ") + hipGetErrorString(e));
+  if (old_nbytes) *old_nbytes = c->pool_len;
+  if (new_nbytes) *new_nbytes = r.refusal == compact::kTooLarge ? r.len : c->pool_len;
+  switch (r.refusal) {
+    case compact::kOutside: return fail(c, SVO_E_INVALID, "svo_pool_compact: a children block the tree reaches lies outside the pool");
+    case compact::kTooDeep: return fail(c, SVO_E_INVALID, "svo_pool_compact: the tree has more levels than the walk supports (or a cycle)");
+    case compact::kTooManyNodes: return fail(c, SVO_E_TOOLARGE, "svo_pool_compact: more reachable nodes than the node lists may hold");
+    case compact::kTooLarge: return fail(c, SVO_E_TOOLARGE, "pool must stay below 2^31 bytes");
+    case compact::kDone: break;
+  }
+  HIPCHK(c, hipEventRecord(s.e1, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  // from here on the pool changes
+  pool_changed(c);
+  (void)hipFree(c->d_pool);
+  c->d_pool = r.pool; c->pool_len = r.len; c->pool_cap = r.cap;
+  if (new_nbytes) *new_nbytes = r.len;
+  s.calls++; s.records = 1u + 8u * r.nodes; s.levels = r.levels;
+  (void)hipEventElapsedTime(&s.gpu_ms, s.e0, s.e1);
+  return refresh_dword0(c);
+}
+
+int svo_compact_info(svo_ctx *c, uint64_t *calls, uint64_t *records, int *levels, float *gpu_ms) {
+  if (!c) return SVO_E_INVALID;
+  if (calls) *calls = c->cs.calls;
+  if (records) *records = c->cs.records;
+  if (levels) *levels = c->cs.levels;
+  if (gpu_ms) *gpu_ms = c->cs.gpu_ms;
   return SVO_OK;
 }
 

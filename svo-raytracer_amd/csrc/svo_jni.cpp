@@ -44,6 +44,20 @@ jlong Java_src_engine_HipRenderer_nBrushInfo(void *, void *, jlong ctx, jlong co
   if (counts_addr) for (int i = 0; i < 4; i++) ((jlong *)(intptr_t)counts_addr)[i] = (jlong)v[i];
   return (jlong)strokes;
 }
+jint Java_src_engine_HipRenderer_nPoolCompact(void *, void *, jlong ctx, jlong sizes_addr) {
+  uint64_t v[2] = {0, 0};
+  const int rc = svo_pool_compact((svo_ctx *)(intptr_t)ctx, &v[0], &v[1]);
+  if (sizes_addr) for (int i = 0; i < 2; i++) ((jlong *)(intptr_t)sizes_addr)[i] = (jlong)v[i];
+  return rc;
+}
+jlong Java_src_engine_HipRenderer_nCompactInfo(void *, void *, jlong ctx, jlong counts_addr, jlong ms_addr) {
+  uint64_t calls = 0, records = 0;
+  int levels = 0;
+  const int rc = svo_compact_info((svo_ctx *)(intptr_t)ctx, &calls, &records, &levels, (float *)(intptr_t)ms_addr);
+  if (rc != SVO_OK) return (jlong)rc;
+  if (counts_addr) { ((jlong *)(intptr_t)counts_addr)[0] = (jlong)records; ((jlong *)(intptr_t)counts_addr)[1] = (jlong)levels; }
+  return (jlong)calls;
+}
 jint Java_src_engine_HipRenderer_nSetCamera(void *, void *, jlong ctx, jfloat px, jfloat py, jfloat pz, jfloat l1x,
                                             jfloat l1y, jfloat l1z, jfloat l2x, jfloat l2y, jfloat l2z, jfloat r1x,
                                             jfloat r1y, jfloat r1z, jfloat r2x, jfloat r2y, jfloat r2z) {
@@ -215,6 +229,12 @@ jint Java_src_engine_HipRenderer_nGroupBrushSphere(void *, void *, jlong g, jint
                                                    jint world_size, jint max_lod, jlong cb_addr) {
   const int org[3] = {ox, oy, oz};
   return svo_group_brush_sphere(GRP(g), org, radius, value, world_size, max_lod, (int32_t *)(intptr_t)cb_addr);
+}
+jint Java_src_engine_HipRenderer_nGroupPoolCompact(void *, void *, jlong g, jlong sizes_addr) {
+  uint64_t v[2] = {0, 0};
+  const int rc = svo_group_pool_compact(GRP(g), &v[0], &v[1]);
+  if (sizes_addr) for (int i = 0; i < 2; i++) ((jlong *)(intptr_t)sizes_addr)[i] = (jlong)v[i];
+  return rc;
 }
 jint Java_src_engine_HipRenderer_nGroupBrushBox(void *, void *, jlong g, jint ox, jint oy, jint oz, jint w, jint h, jint d, jint value,
                                                 jint world_size, jint max_lod, jlong cb_addr) {

@@ -24,6 +24,7 @@ EXPORTS = [
     "svo_ipc_export", "svo_ipc_open", "svo_ipc_close", "svo_set_sequence", "svo_ring_submit_cams",
     "svo_build_from_heightmap16", "svo_launch_info",
     "svo_pool_download_range", "svo_brush_sphere", "svo_brush_box", "svo_brush_info", "svo_group_brush_sphere", "svo_group_brush_box",
+    "svo_pool_compact", "svo_compact_info", "svo_group_pool_compact",
     "svo_group_create", "svo_group_destroy", "svo_group_last_error", "svo_group_size", "svo_group_member", "svo_group_pool_upload",
     "svo_group_pool_update", "svo_group_pool_download", "svo_group_build_from_heightmap", "svo_group_set_camera",
     "svo_group_set_params", "svo_group_set_pipeline", "svo_group_set_tuning", "svo_group_set_progressive", "svo_group_set_sequence",
@@ -78,6 +79,9 @@ def lib(path=None):
         L.svo_brush_info.argtypes = [vp] + [ctypes.POINTER(u64)] * 5 + [fp]
         L.svo_group_brush_sphere.argtypes = [vp, vp] + [ci] * 4 + [vp]
         L.svo_group_brush_box.argtypes = [vp, vp] + [ci] * 6 + [vp]
+        L.svo_pool_compact.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.svo_compact_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci), fp]
+        L.svo_group_pool_compact.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
         L.svo_pool_reserve.argtypes = [vp, u64]
         L.svo_pool_upload_device.argtypes = [vp, vp, u64]
         L.svo_build_from_heightmap.argtypes = [vp, vp, vp, ci, ctypes.POINTER(u64)]
@@ -249,6 +253,12 @@ class HipGroup:
                                               int(max_lod), cb.ctypes.data))
         return [int(v) for v in cb]
 
+    def pool_compact(self):
+        """svo_group_pool_compact: every member's replica rewritten as its reachable records; returns (bytes before, after)"""
+        old, new = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.svo_group_pool_compact(self._h, ctypes.byref(old), ctypes.byref(new)))
+        return int(old.value), int(new.value)
+
     def build_from_heightmap(self, height, material):
         height = np.ascontiguousarray(height, dtype=np.uint16)
         material = np.ascontiguousarray(material, dtype=np.uint8)
@@ -396,6 +406,19 @@ class HipContext:
         self._chk(self._L.svo_brush_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(ms)))
         return {"strokes": int(v[0].value), "visited": int(v[1].value), "subdivided": int(v[2].value), "lo": int(v[3].value),
                 "hi": int(v[4].value), "gpu_ms": float(ms.value)}
+
+    def pool_compact(self):
+        """svo_pool_compact: the device pool rewritten as exactly its reachable records, in the builder's order; returns
+        (bytes before, bytes after).  Every byte offset into the old pool is void afterwards."""
+        old, new = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.svo_pool_compact(self._h, ctypes.byref(old), ctypes.byref(new)))
+        return int(old.value), int(new.value)
+
+    def compact_info(self):
+        """what compaction did (svo_compact_info): calls so far; of the last one the records copied, the levels, its GPU time"""
+        calls, records, levels, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int(), ctypes.c_float()
+        self._chk(self._L.svo_compact_info(self._h, ctypes.byref(calls), ctypes.byref(records), ctypes.byref(levels), ctypes.byref(ms)))
+        return {"calls": int(calls.value), "records": int(records.value), "levels": int(levels.value), "gpu_ms": float(ms.value)}
 
     def pool_upload_device(self, dptr, nbytes):
         self._chk(self._L.svo_pool_upload_device(self._h, ctypes.c_void_p(int(dptr)), int(nbytes)))

@@ -4,7 +4,8 @@ below it.  Three figures per stroke:
   gpu_ms    svo_brush_sphere / svo_brush_box on the device pool (svo_brush_info: planning + writing, without the table)
   cpu_ms    the restatement of Octree.useSDFBrush (oracle/octree_restatement.cpp) on a host copy of the same pool
   route_ms  today's route: the restatement + the two svo_pool_update calls (wall)
-and the wall time of the GPU call (with the descriptor table following).  A measurement script (it loads the oracle-side
+and the wall time of the GPU call (with the descriptor table following).  Then svo_pool_compact on what the strokes left:
+lengths before and after, GPU and wall time, records and levels (svo_compact_info).  A measurement script (it loads the oracle-side
 restatement), not product code.  --md FILE writes the table as markdown."""
 import os
 import sys
@@ -32,6 +33,26 @@ def crosshair(ctx, h):
     pick = tuple(int(v) for v in p)
     x, z = int(np.clip(p[0], 200, N - 200)), int(np.clip(p[2], 200, N - 200))
     return pick, (x, int(h[z, x]), z), float(depth)
+
+
+def compact_leg(gpu):
+    """svo_pool_compact on the pool the strokes left, and once more on its own result (which must come back as it is); the K0
+    frame before and after must agree in everything but the hit records' pointers"""
+    cam = CAMERAS["K0"]
+    before = gpu.render(None, 1920, 1080, cam, 2, 0)
+    out = ["| call | bytes before | bytes after | gpu_ms | call wall ms | records | levels |", "|---|---|---|---|---|---|---|"]
+    for call in ("after the strokes", "again"):
+        t0 = time.perf_counter()
+        old, new = gpu.pool_compact()
+        wall_ms = (time.perf_counter() - t0) * 1e3
+        info = gpu.compact_info()
+        out.append("| %s | %d | %d | %.3f | %.3f | %d | %d |" % (call, old, new, info["gpu_ms"], wall_ms, info["records"], info["levels"]))
+    after = gpu.render(None, 1920, 1080, cam, 2, 0)
+    same = (before["rgba"] == after["rgba"]).all() and (before["depth"].view(np.uint32) == after["depth"].view(np.uint32)).all() and all(
+        (before["hits"][k] == after["hits"][k]).all() for k in ("value", "raw_normal", "level", "iter"))
+    out += ["", "K0 frame (1920x1080, mode 0) equal before and after but for the pointers: %s; pixels whose pointer moved: %d" % (
+        bool(same), int((before["hits"]["pointer"] != after["hits"]["pointer"]).sum()))]
+    return out
 
 
 def main():
@@ -71,6 +92,7 @@ def main():
              "|---|---|---|---|---|---|---|---|---|---|---|---|"]
     for r in rows:
         lines.append("| %s | %s | %s %s | %d | %.3f | %.3f | %.3f | %.3f | %d | %d | %d | %s |" % r)
+    lines += ["", "svo_pool_compact after these strokes:", ""] + compact_leg(gpu)
     print("\n".join(lines))
     if md:
         open(md, "w").write("\n".join(lines) + "\n")

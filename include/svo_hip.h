@@ -176,6 +176,21 @@ int svo_set_tuning(svo_ctx *ctx, int waves_per_cu, int round_threshold_sixteenth
 /* shape of the last pipeline-1 launch of the context: persistent waves launched, waves per CU they were sized by, round
  * threshold in sixteenths (any pointer may be NULL).  Diagnostic: what svo_set_tuning's automatic choice resolved to. */
 int svo_launch_info(svo_ctx *ctx, int *waves, int *waves_per_cu, int *round_threshold_sixteenths);
+/* The primary-hit cache of a still camera (default on).  A static-camera batch of mode 0 (svo_set_batch / svo_ring_submit with
+ * more than one frame, at least 2 bounces, one sample per pixel, no beam pre-pass, hit records off) casts a pixel's primary ray
+ * once for its frames; consecutive such submissions under one camera, pool and frame cast the very same primary rays, so the
+ * library keeps the hits of one submission (the fill) and later submissions shade from them without casting (reuse).  Same
+ * bytes.  The key is everything a primary hit depends on: the pool (any upload, update, brush stroke, compaction, build or
+ * commit empties the cache), the 15 camera floats by bits, the frame's size, the row range / stripes.  frameNumber, bounces,
+ * the mirror mask and the outputs are not part of it.  The library never waits for the cache: a submission whose camera differs
+ * runs as before, a fill starts once the launches of the old view have drained, reuse starts with the first submission after
+ * the fill has completed.  Cost: 48 bytes of device memory per pixel of the rows a launch renders (100 MB at 1080p), allocated
+ * at the first fill and freed by svo_resize / svo_destroy; when the allocation fails the submissions run as before, without an
+ * error.  enabled = 0 empties the cache and keeps every submission on the kernels that cast their primaries. */
+int svo_set_primary_cache(svo_ctx *ctx, int enabled);
+/* *fills / *reuses = launches that wrote / read the cache since the context was made, *bytes = device memory it holds,
+ * *state = 0 empty, 1 filling (the fill has not been seen complete), 2 ready.  Any may be NULL.  Never waits. */
+int svo_primary_cache_info(svo_ctx *ctx, uint64_t *fills, uint64_t *reuses, uint64_t *bytes, int *state);
 /* the reference's dormant cross-frame accumulation (commented out at svotrace.comp:712-719; MAX_FRAME_ITER :43):
  * when enabled and frameNumber > 1, a pixel's colour becomes (frameNumber * last + colour) / (frameNumber + 1), `last`
  * being what the colour image holds from the previous dispatch (rgba8, as imageLoad returns it), and stays `last` from

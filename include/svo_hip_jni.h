@@ -107,6 +107,10 @@ jint Java_src_engine_HipRenderer_nSetTuning(void *env, void *cls, jlong ctx, jin
 /* svo_launch_info: persistent waves of the last pipeline-1 launch (what the automatic launch shape resolved to); waves per
  * CU through the address (0 = not wanted) */
 jint Java_src_engine_HipRenderer_nLaunchInfo(void *env, void *cls, jlong ctx, jlong waves_per_cu_addr);
+jint Java_src_engine_HipRenderer_nSetPrimaryCache(void *env, void *cls, jlong ctx, jint enabled);
+/* svo_primary_cache_info: the cache's state (0 empty, 1 filling, 2 ready) or a negative status; three longs (fills, reuses,
+ * bytes) at the address unless 0 */
+jint Java_src_engine_HipRenderer_nPrimaryCacheInfo(void *env, void *cls, jlong ctx, jlong counts_addr);
 jint Java_src_engine_HipRenderer_nSetDerived(void *env, void *cls, jlong ctx, jint mode);
 jint Java_src_engine_HipRenderer_nSetHitRecords(void *env, void *cls, jlong ctx, jint enabled);
 jint Java_src_engine_HipRenderer_nSetRows(void *env, void *cls, jlong ctx, jint y0, jint y1);

@@ -494,6 +494,21 @@ public class HipRenderer {
     return n;
   }
 
+  /** The primary-hit cache of a still camera (default on; 48 bytes of device memory per pixel): off = every submission casts its primaries. */
+  public void setPrimaryCache(boolean on) {
+    check(nSetPrimaryCache(ctx, on ? 1 : 0));
+  }
+
+  /** State of the primary-hit cache (0 empty, 1 filling, 2 ready), or a negative status; counts[0..2] = fills, reuses, bytes. */
+  public int primaryCacheInfo(long[] counts) {
+    ByteBuffer w = MemoryUtil.memAlloc(24);
+    int state = nPrimaryCacheInfo(ctx, MemoryUtil.memAddress(w));
+    for (int i = 0; counts != null && i < counts.length && i < 3; i++)
+      counts[i] = w.getLong(8 * i);
+    MemoryUtil.memFree(w);
+    return state;
+  }
+
   /** 0 = walk the pool's records as the shader does, 1 (default) = the interior-descriptor table when the pool allows */
   public void setDerived(int mode) {
     check(nSetDerived(ctx, mode));
@@ -753,6 +768,8 @@ public class HipRenderer {
   private static native int nSetPipeline(long ctx, int pipeline);
   private static native int nSetTuning(long ctx, int wavesPerCu, int roundThresholdSixteenths);
   private static native int nLaunchInfo(long ctx, long wavesPerCuAddr);
+  private static native int nSetPrimaryCache(long ctx, int enabled);
+  private static native int nPrimaryCacheInfo(long ctx, long countsAddr);
   private static native int nSetDerived(long ctx, int mode);
   private static native int nSetHitRecords(long ctx, int enabled);
   private static native int nSetRows(long ctx, int y0, int y1);

@@ -205,7 +205,10 @@ static hipError_t alloc_planes(size_t n_elems, bool want_hits, Planes &out) {
 // every pool mutator starts here, before its argument checks: the pool is about to change (or to be handed out for writing), so
 // what was derived from it no longer describes it
 static void pool_changed(svo_ctx *c) {
-  if (c) { c->beam_live_valid = false; c->derived_valid = false; }
+  if (c) {
+    c->beam_live_valid = false; c->derived_valid = false;
+    c->pb.pool_epoch++; persist_kept_drop(c->pb);   // the primary-hit cache: part of its key, and empty from here on
+  }
 }
 
 // waits for the frames in flight on every set's stream
@@ -778,6 +781,23 @@ int svo_launch_info(svo_ctx *c, int *waves, int *waves_per_cu, int *round_thresh
   if (waves) *waves = c->pb.last_blocks;
   if (waves_per_cu) *waves_per_cu = c->pb.last_per_cu;
   if (round_threshold_sixteenths) *round_threshold_sixteenths = c->pb.last_thresh;
+  return SVO_OK;
+}
+
+int svo_set_primary_cache(svo_ctx *c, int enabled) {
+  if (!c) return SVO_E_INVALID;
+  c->pb.kept_mode = enabled != 0 ? 1 : 0;
+  if (!enabled) persist_kept_drop(c->pb);
+  return SVO_OK;
+}
+
+int svo_primary_cache_info(svo_ctx *c, uint64_t *fills, uint64_t *reuses, uint64_t *bytes, int *state) {
+  if (!c) return SVO_E_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (fills) *fills = c->pb.kept_fills;
+  if (reuses) *reuses = c->pb.kept_reuses;
+  if (bytes) *bytes = (uint64_t)c->pb.kept_cap * 3 * sizeof(uint4);
+  if (state) *state = !c->pb.kept_valid ? 0 : (persist_kept_filled(c->pb) ? 2 : 1);
   return SVO_OK;
 }
 

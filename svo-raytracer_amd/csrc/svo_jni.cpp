@@ -141,6 +141,13 @@ jint Java_src_engine_HipRenderer_nLaunchInfo(void *, void *, jlong ctx, jlong wa
   const int rc = svo_launch_info(CTX(ctx), &waves, (int *)(intptr_t)waves_per_cu_addr, nullptr);
   return rc == SVO_OK ? (jint)waves : (jint)rc;
 }
+jint Java_src_engine_HipRenderer_nSetPrimaryCache(void *, void *, jlong ctx, jint enabled) { return svo_set_primary_cache(CTX(ctx), enabled); }
+jint Java_src_engine_HipRenderer_nPrimaryCacheInfo(void *, void *, jlong ctx, jlong counts_addr) {
+  uint64_t *n = (uint64_t *)(intptr_t)counts_addr;
+  int state = 0;
+  const int rc = svo_primary_cache_info(CTX(ctx), n, n ? n + 1 : nullptr, n ? n + 2 : nullptr, &state);
+  return rc == SVO_OK ? (jint)state : (jint)rc;
+}
 jint Java_src_engine_HipRenderer_nSetDerived(void *, void *, jlong ctx, jint mode) { return svo_set_derived(CTX(ctx), mode); }
 jint Java_src_engine_HipRenderer_nSetHitRecords(void *, void *, jlong ctx, jint enabled) { return svo_set_hit_records(CTX(ctx), enabled); }
 jint Java_src_engine_HipRenderer_nSetRows(void *, void *, jlong ctx, jint y0, jint y1) { return svo_set_rows(CTX(ctx), y0, y1); }

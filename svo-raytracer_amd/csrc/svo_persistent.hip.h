@@ -77,6 +77,11 @@ struct PersistArgs {
   // 1 = a band slot is a pixel with all the frames of the batch (persist_span_kernel): chosen once, in persist_launch
   int span;
   uint4 *prim;          // ... and the primary-hit records of its lanes, kSpanWords words per persistent lane of the launch
+  // the context's primary-hit cache (persist_kept_kernel): three planes of kept_n records, a pixel's at its frame-0 output index
+  // less kept_origin (the output index of the launch's first pixel row)
+  uint4 *kept;          // null: the launch does not use the cache
+  uint32_t kept_n, kept_origin;
+  int kept_fill;        // 1 = this launch writes the cache (persist_kept_kernel<true>), 0 = it reads it
 };
 
 // n / d by multiply-high with m = ceil(2^32 / d) = (2^32 + e) / d, 0 <= e < d (made on the host, udiv_magic): with
@@ -281,9 +286,13 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 // own random number -- the same operations on the same values in the same order as the (frame, pixel) slots, so the same bytes.
 constexpr uint32_t kSpanWords = 12;   // three uint4 per persistent lane, [wave][3][lane]
 constexpr uint32_t kSpanSun = 1u << 16;   // in a kSpan lane's `seg`: a miss of the segment under way adds the sun's light
-template <int kMode, class Walk, bool kCams, bool kTab, bool kSpan>
+constexpr uint32_t kKeptMiss = 1u;        // in the last word of a cached record's third plane: the primary ray left the octree
+// kKept (persist_kept_kernel<true>, the fill): the kSpan kernel with a pixel's record in the context's cache (a.kept) instead of
+// its lane's own, and a record for the primaries that leave the octree too.
+template <int kMode, class Walk, bool kCams, bool kTab, bool kSpan, bool kKept = false>
 __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk::Stack &stk) {
   static_assert(!kSpan || (kMode == 0 && !kCams), "a batch shares its primary ray only in mode 0 with one camera");
+  static_assert(!kKept || kSpan, "the cache keeps the primary hits of a kSpan launch");
   const uint32_t lane = threadIdx.x;
   const Frame &f = a.f;
   Walk walk;
@@ -353,16 +362,23 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
         // (the address is formed here, in the round: hoisted in front of the kernel's loop it is two registers spilled for good)
         uint32_t rl = lane;
         asm volatile("" : "+v"(rl));
-        uint4 *const rec = a.prim + (size_t)blockIdx.x * (64u * kSpanWords / 4u) + rl;   // [3][64] uint4 per wave
+        // (kKept: the pixel's record in the cache; `pix` is frame (seg >> 24)'s output index here)
+        uint4 *const rec = kKept ? a.kept + (pix - (seg >> 24) * f.frame_stride - a.kept_origin)
+                                 : a.prim + (size_t)blockIdx.x * (64u * kSpanWords / 4u) + rl;   // [3][64] uint4 per wave
+        const uint32_t rs = kKept ? a.kept_n : 64u;   // records between two planes
         const V3 sun = normalize3(mk(1.0f, 1.0f, 1.0f));
         bool shade = true;
         if (segn == 0u) {
           if (c.hit) {   // the pixel's primary hit, for all its frames
             rec[0] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(c.t));
-            rec[64] = make_uint4(__float_as_uint(c.voxel_pos.x), __float_as_uint(c.voxel_pos.y), __float_as_uint(c.voxel_pos.z), c.value);
-            rec[128] = make_uint4(__float_as_uint(c.normal.x), __float_as_uint(c.normal.y), __float_as_uint(c.normal.z), 0u);
+            rec[rs] = make_uint4(__float_as_uint(c.voxel_pos.x), __float_as_uint(c.voxel_pos.y), __float_as_uint(c.voxel_pos.z), c.value);
+            rec[2u * rs] = make_uint4(__float_as_uint(c.normal.x), __float_as_uint(c.normal.y), __float_as_uint(c.normal.z), 0u);
             emit = false;
           } else {
+            if (kKept) {   // a miss is kept too: the direction its sky is a function of, and the flag (kKeptMiss)
+              rec[0] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), 0u);
+              rec[2u * rs] = make_uint4(0u, 0u, 0u, kKeptMiss);
+            }
             const V3 s = sky_colour(d);
             ecol = mk(0.0f + s.x, 0.0f + s.y, 0.0f + s.z);
             shade = false;
@@ -382,7 +398,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
           const uint32_t fi = (seg >> 24) + 1u;
           shade = fi < (uint32_t)f.batch;
           if (shade) {   // the pixel's next frame: a refilled lane's path state, the primary hit as it was
-            const uint4 r0 = rec[0], r1 = rec[64], r2 = rec[128];
+            const uint4 r0 = rec[0], r1 = rec[rs], r2 = rec[2u * rs];
             d = mk(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
             c.t = __uint_as_float(r0.w);
             c.voxel_pos = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
@@ -733,6 +749,175 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_span_k
   persist_body<0, DescWalk, false, kTab, true>(a, stk);
 }
 
+#if SVO_BAND_COLMAJOR
+// The reuse of the context's primary-hit cache (persist_kept_kernel<false>): the kSpan kernel of a launch whose primary hits an
+// earlier launch of the same camera, pool and frame left in a.kept (the fill).  A refilled lane casts nothing: it loads its
+// pixel's record and shades frame 0 from it exactly as the kSpan kernel shades frames 1.. from its lane's own -- the same
+// operations on the same values in the same order, so the same bytes.  The round's order differs: the lanes whose frame ended
+// emit first, then slots are drawn and records loaded (a miss emits its sky into every frame and its lane draws again in the same
+// round, while the band has slots), and only then ONE shading pass runs for the lanes holding a primary hit from a record or
+// an inner hit from the cast: no refilled lane sits out a traversal phase waiting for the next round's shading.
+// Mode 0, the descriptor walk, the row / column tables, one slot per pixel.
+__device__ __forceinline__ void persist_reuse_body(const PersistArgs &a, DescWalk::Stack &stk) {
+  const uint32_t lane = threadIdx.x;
+  const Frame &f = a.f;
+  DescWalk walk;
+  walk.setup(a);
+  const V3 sun = normalize3(mk(1.0f, 1.0f, 1.0f));
+
+  DescWalk::State t;
+  int status = ST_IDLE;
+  uint32_t pix = 0, seg = 0;   // seg: path segment in the low byte, kSpanSun, the frame the lane's pixel has reached in bits 24..
+  int px = 0, py = 0;
+  V3 d = mk(0.f, 0.f, 0.f), mask = mk(1.f, 1.f, 1.f), accum = mk(0.f, 0.f, 0.f);
+  float r = 0.0f;
+
+  uint32_t band = xcc_id();
+  int bands_left = 8;
+
+  for (;;) {
+    // ---------------- finished lanes: a path that ended stores its pixel and goes on to the pixel's next frame; an inner hit waits
+    // for the shading pass
+    bool shade = false, load = false;
+    V3 hpos = mk(0.f, 0.f, 0.f), hnormal = mk(0.f, 0.f, 0.f);
+    uint32_t hvalue = 0u;
+    if (status >= ST_HIT) {
+      const Cast c = walk.result(t, status);
+      const uint32_t segn = seg & 0xffu;   // (never 0: no lane of this kernel casts a primary ray)
+      if (!c.hit || (int)segn + 1 >= f.bounces) {   // frame (seg >> 24)'s path ends
+        float edepth = 0.0f;
+        if (c.hit) {
+          accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
+          edepth = c.t;
+        } else {
+          if ((seg & kSpanSun) != 0u) accum = mk(accum.x + mask.x * 7.0f, accum.y + mask.y * 7.0f, accum.z + mask.z * 7.0f);
+          accum = mk(accum.x + mask.x * 1.0f, accum.y + mask.y * 1.0f, accum.z + mask.z * 1.0f);
+        }
+        persist_emit(a, pix, 0u, px, py, accum, edepth);
+        const uint32_t fi = (seg >> 24) + 1u;
+        if (fi < (uint32_t)f.batch) {   // keeps its pixel
+          seg = fi << 24;
+          pix += f.frame_stride;
+          load = true;
+          status = ST_ACTIVE;
+        } else {
+          status = ST_IDLE;
+        }
+      } else {
+        hpos = c.voxel_pos; hnormal = c.normal; hvalue = c.value;
+        shade = true;
+        status = ST_ACTIVE;   // not idle: keeps its pixel (the set-up below gives the real status)
+      }
+    }
+
+    // ---------------- idle lanes draw pixels (ballot + prefix count, one atomic per wave: persist_body's walk of the bands with a
+    // pixel per slot), then every lane at the start of a frame loads its pixel's record
+    for (;;) {
+      bool again = false;   // the band still has slots behind this draw
+      const unsigned long long idle = bands_left > 0 ? __ballot(status == ST_IDLE) : 0ull;
+      if (idle != 0ull) {
+        const uint32_t n = (uint32_t)__builtin_popcountll(idle);
+        const int leader = __builtin_ctzll(idle);
+        const int first_row = (int)band * a.rows_per_band;
+        int band_rows = f.tiles_y - first_row;
+        band_rows = band_rows < 0 ? 0 : (band_rows > a.rows_per_band ? a.rows_per_band : band_rows);
+        const uint32_t band_total = (uint32_t)(band_rows * f.tiles_x) * 64u;
+        uint32_t base = 0;
+        if ((int)lane == leader) base = atomicAdd(a.heads + band * kHeadStride, n);
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+        const uint32_t slot =
+            base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+        if (status == ST_IDLE && slot < band_total) {
+          const uint32_t l = slot & 63u, q = slot >> 6;
+          const int full_band = band_rows == a.rows_per_band ? 0 : 1;
+          int tile_x = (int)udiv_by(q, (uint32_t)band_rows, a.mg_rows[full_band]);
+          const int tile_y = first_row + ((int)q - tile_x * band_rows);
+          if (a.reverse) tile_x = f.tiles_x - 1 - tile_x;
+          px = tile_x * 8 + (int)(l & 7u);
+          py = frame_gy(f, tile_y, (int)(l >> 3));
+          if (px < f.width && py < f.y1 && py < f.height) {
+            pix = (uint32_t)frame_oy(f, tile_y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px;
+            seg = 0u;
+            load = true;
+            status = ST_ACTIVE;   // taken
+          }
+        }
+        if (base + n >= band_total) {   // this band is used up: the next one in the next round (work stealing)
+          band = (band + 1u) & 7u;
+          bands_left--;
+        } else {
+          again = true;
+        }
+      }
+      if (load) {
+        const uint32_t fi = seg >> 24;
+        const uint4 *const rec = a.kept + (pix - fi * f.frame_stride - a.kept_origin);
+        const uint4 r0 = rec[0], r1 = rec[a.kept_n], r2 = rec[2u * a.kept_n];
+        load = false;
+        d = mk(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
+        if (r2.w == kKeptMiss) {   // (of a new pixel only: a pixel with a frame behind it hit) the same sky in every frame
+          const V3 s = sky_colour(d);
+          const V3 ecol = mk(0.0f + s.x, 0.0f + s.y, 0.0f + s.z);
+          for (int k = 0; k < f.batch; k++) persist_emit(a, pix + (uint32_t)k * f.frame_stride, 0u, px, py, ecol, 0.0f);
+          status = ST_IDLE;
+        } else {   // the primary hit as it was (its t is no input of the shading), and frame fi's random number
+          hpos = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
+          hvalue = r1.w;
+          hnormal = mk(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z));
+          mask = mk(1.f, 1.f, 1.f);
+          accum = mk(0.f, 0.f, 0.f);
+          const float *fr = a.rc + (size_t)fi * a.rc_stride;
+          const float colx = fr[2 * px], roww = fr[((2 * f.width + 3) & ~3) + 8 * py + 3];
+          r = rand_of_dot(((float)px + colx) * 12.9898f + ((float)py + roww) * 78.233f);
+          shade = true;
+        }
+      }
+      if (!again || __ballot(status == ST_IDLE) == 0ull) break;
+    }
+
+    // ---------------- one shading pass: a hit the path goes on from (persist_launch: f.bounces >= 2), persist_body's kSpan shading
+    bool ninit = false;
+    if (shade) {
+      const bool mirror = ((f.mirror_mask >> (hvalue & 31u)) & 1u) != 0u;
+      const V3 nd = scatter(d, hnormal, r, mirror);
+      const V3 mc = material_colour(hvalue, mk(hpos.x - 1.0f, hpos.y - 1.0f, hpos.z - 1.0f));
+      accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
+      mask = mk(mask.x * mc.x, mask.y * mc.y, mask.z * mc.z);
+      const float k = dot3(nd, hnormal);
+      mask = mk(mask.x * k, mask.y * k, mask.z * k);
+      d = nd;
+      seg++;
+      ninit = true;
+      const V3 nd2 = scatter(d, hnormal, r, mirror);   // kSpanSun: what a miss of the new ray will add
+      seg = acos_pinned(dot3(nd2, sun)) < 0.4f ? (seg | kSpanSun) : (seg & ~kSpanSun);
+    }
+    // ---------------- set up the new rays
+    if (ninit) {
+      status = walk.init(t, hpos, d, true, 0.0f);
+      walk.fresh_stack(stk, lane);
+    }
+    if (__ballot(status != ST_IDLE) == 0ull) {
+      if (bands_left > 0) continue;
+      break;
+    }
+    // ---------------- traverse until enough lanes have stopped to make a round worthwhile (persist_body)
+    const int active0 = __builtin_popcountll(__ballot(status == ST_ACTIVE));
+    const int drained = (active0 * SVO_DRAIN_NUM) / 16 < active0 - 1 ? (active0 * SVO_DRAIN_NUM) / 16 : (active0 > 0 ? active0 - 1 : 0);
+    const int threshold = __builtin_amdgcn_readfirstlane(bands_left > 0 ? (active0 * a.thresh_num) / 16 : drained);
+    walk.run(stk, lane, t, status, __ballot(status == ST_ACTIVE), threshold, ~0ull, nullptr);
+  }
+}
+
+// a static-camera batch of mode 0 whose primary hits stay in the context's cache from launch to launch (persist_launch chooses):
+// kFill = the kSpan kernel writing the cache, !kFill = the kernel that reads it and casts no primary ray
+template <bool kFill>
+__global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_kept_kernel(const PersistArgs a) {
+  __shared__ DescWalk::Stack stk;
+  if constexpr (kFill) persist_body<0, DescWalk, false, true, true, true>(a, stk);
+  else persist_reuse_body(a, stk);
+}
+#endif
+
 // a.fold > 1: tiles per group of a band's walk.  1 / 8 / 64 / 512 / all: 4.47 / 4.49 / 4.47 / 4.41 / 4.20 Grays/s at 64
 // samples per pixel (tools/history/r03_fold2.sh): a group's samples should be in flight together, not a whole band's
 constexpr int kFoldGroup = 8;
@@ -775,8 +960,29 @@ struct PersistBuffers {
                        // SVO_BATCH_PRIMARY=0: every frame of the batch casts its own
   uint4 *prim[8] = {};         // primary-hit records of persist_span_kernel's lanes, one buffer per counter set
   size_t prim_waves = 0;       // persistent waves each of them has room for
+  // The primary-hit cache (persist_kept_kernel): ONE buffer for the context, whatever counter set a launch runs on.  What a
+  // primary hit depends on is its key; a launch whose key equals the cache's reads it once the fill has been SEEN complete
+  // (hipEventQuery; nothing here ever waits), a launch with another key fills it once the buffer is idle -- the last fill and
+  // every launch that read it seen complete -- and every other launch runs persist_span_kernel as before.
+  struct KeptKey {
+    const uint8_t *pool; const uint2 *desc;
+    uint64_t pool_epoch;
+    uint32_t pool_len, cam[15];
+    int32_t width, height, y0, y1, row_step, out_y0, tiles_y;
+  };
+  int kept_mode = 1;           // svo_set_primary_cache
+  uint4 *kept = nullptr;
+  size_t kept_cap = 0;         // records per plane the buffer has room for
+  size_t kept_failed = 0;      // ... and the size hipMalloc last refused: launches of that size and larger stay on persist_span_kernel
+  KeptKey kept_key = {};
+  bool kept_valid = false;     // kept_key describes the last fill (cleared by persist_kept_drop)
+  bool kept_fill_inflight = false;   // a fill was launched and kept_filled not yet seen complete
+  hipEvent_t kept_filled = nullptr;
+  bool kept_reader[kHeadSets] = {};  // the set's head_done is behind a launch that read the cache (or behind one that waited for it)
+  uint64_t pool_epoch = 0;     // bumped by everything that changes the pool (svo_hip.hip::pool_changed)
+  uint64_t kept_fills = 0, kept_reuses = 0;
   int last_thresh = 9;
-  int waves_per_cu = 0;      // 0 = automatic: as many as fit (occupancy query) for one launch at a time, kRingWavesPerCu for
+  int waves_per_cu = 0;     // 0 = automatic: as many as fit (occupancy query) for one launch at a time, kRingWavesPerCu for
                              // the submissions of a ring with more than one slot (in_ring, set around the launch by ring_submit)
   bool in_ring = false;
   bool in_overlap = false;   // set around the launch by svo_dispatch_async while it takes turns on several image sets ...
@@ -796,11 +1002,41 @@ inline void persist_free(PersistBuffers &b) {
   for (auto &f : b.facc) if (f) (void)hipFree(f);
   for (auto &e : b.head_done) if (e) (void)hipEventDestroy(e);
   for (auto &e : b.facc_done) if (e) (void)hipEventDestroy(e);
+  if (b.kept) (void)hipFree(b.kept);
+  if (b.kept_filled) (void)hipEventDestroy(b.kept_filled);
   const int wpc = b.waves_per_cu, th = b.thresh_num, sm = b.spare_mode, tm = b.table_mode;   // tuning survives a resize
   const float4 *nt = b.ntab;
-  const int nm = b.ntab_mode, sp = b.span_mode;
+  const int nm = b.ntab_mode, sp = b.span_mode, km = b.kept_mode;
+  const uint64_t ep = b.pool_epoch, kf = b.kept_fills, kr = b.kept_reuses;   // (so do the counts svo_primary_cache_info reports)
   b = PersistBuffers();
   b.waves_per_cu = wpc; b.thresh_num = th; b.spare_mode = sm; b.table_mode = tm; b.ntab = nt; b.ntab_mode = nm; b.span_mode = sp;
+  b.kept_mode = km; b.pool_epoch = ep; b.kept_fills = kf; b.kept_reuses = kr;
+}
+
+// the cache describes nothing any more (the pool changed, the host opted out).  The buffer and what is known about the launches
+// still using it stay: the next fill waits its turn like any other.
+inline void persist_kept_drop(PersistBuffers &b) { b.kept_valid = false; }
+
+// has `ev` completed?  Never waits; hipErrorNotReady is no error and does not stay behind as one.
+inline bool persist_event_done(hipEvent_t ev) {
+  const hipError_t e = hipEventQuery(ev);
+  if (e == hipErrorNotReady) (void)hipGetLastError();
+  return e == hipSuccess;
+}
+// has the last fill been seen complete?  (true when there never was one)
+inline bool persist_kept_filled(PersistBuffers &b) {
+  if (b.kept_fill_inflight && persist_event_done(b.kept_filled)) b.kept_fill_inflight = false;
+  return !b.kept_fill_inflight;
+}
+// ... and every launch that read the cache?
+inline bool persist_kept_idle(PersistBuffers &b) {
+  if (!persist_kept_filled(b)) return false;
+  bool idle = true;
+  for (int i = 0; i < kHeadSets; i++) {
+    if (b.kept_reader[i] && persist_event_done(b.head_done[i])) b.kept_reader[i] = false;
+    idle = idle && !b.kept_reader[i];
+  }
+  return idle;
 }
 
 // The row / column tables of a launch: per frame of the batch W + H threads.  A handful of workgroups: unlike a kernel of one
@@ -880,6 +1116,13 @@ inline void persist_launch_mode(const PersistArgs &a, int blocks, hipStream_t st
   if (a.spare) { persist2_launch_mode<kMode>(a, blocks, stream); return; }
 #endif
   if (kMode == 0 && a.span) {   // (persist_launch: mode 0, one camera, the descriptor walk; any other mode runs its own kernel)
+#if SVO_BAND_COLMAJOR
+    if (a.kept) {   // (persist_launch: only with the tables)
+      if (a.kept_fill) hipLaunchKernelGGL((persist_kept_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+      else hipLaunchKernelGGL((persist_kept_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
+      return;
+    }
+#endif
     if (a.rc) hipLaunchKernelGGL((persist_span_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((persist_span_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
     return;
@@ -1117,6 +1360,34 @@ inline int persist_launch(PersistBuffers &b, const uint8_t *pool, const Frame &f
     }
     a.rc = b.rc[hset]; a.rc_stride = (uint32_t)stride;
   }
+  // the primary-hit cache: static-camera batches without hit records (those would need a fourth plane), on the tables' kernels
+  a.kept = nullptr; a.kept_n = 0; a.kept_origin = 0; a.kept_fill = 0;
+  if (SVO_BAND_COLMAJOR && span && b.kept_mode != 0 && f.write_hits == 0 && a.rc != nullptr) {
+    PersistBuffers::KeptKey key;
+    memset(&key, 0, sizeof key);
+    key.pool = pool; key.desc = desc; key.pool_epoch = b.pool_epoch; key.pool_len = f.pool_len;
+    memcpy(key.cam, f.cam, sizeof key.cam);
+    key.width = f.width; key.height = f.height; key.y0 = f.y0; key.y1 = f.y1; key.row_step = f.row_step; key.out_y0 = f.out_y0;
+    key.tiles_y = f.tiles_y;
+    const size_t need = (size_t)f.tiles_y * 8 * (size_t)f.width;   // a record per pixel of the rows the launch writes
+    if (b.kept_valid && memcmp(&key, &b.kept_key, sizeof key) == 0) {
+      if (persist_kept_filled(b)) a.kept = b.kept;
+    } else if ((b.kept_failed == 0 || need < b.kept_failed) && need < (1ull << 30) && persist_kept_idle(b)) {
+      b.kept_valid = false;
+      if (!b.kept_filled && hipEventCreateWithFlags(&b.kept_filled, hipEventDisableTiming) != hipSuccess) {
+        b.kept_filled = nullptr;
+        (void)hipGetLastError();
+      } else if (b.kept_cap < need) {   // (idle, so nothing reads the old buffer; the wait is the one `prim` grows behind)
+        if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;
+        if (b.kept) (void)hipFree(b.kept);
+        b.kept = nullptr; b.kept_cap = 0;
+        if (hipMalloc((void **)&b.kept, 3 * need * sizeof(uint4)) == hipSuccess) b.kept_cap = need;
+        else { b.kept = nullptr; b.kept_failed = need; (void)hipGetLastError(); }   // no room: today's kernel, and no error
+      }
+      if (b.kept_filled && b.kept_cap >= need) { a.kept = b.kept; a.kept_fill = 1; b.kept_key = key; }
+    }
+    a.kept_n = (uint32_t)b.kept_cap; a.kept_origin = (uint32_t)f.out_y0 * (uint32_t)f.width;
+  }
   if (b.head_used[hset] && (e = hipStreamWaitEvent(stream, b.head_done[hset], 0)) != hipSuccess) return (int)e;
   for (int s = 0; s < (fold > 1 ? 1 : spp); s++) {
     a.reverse = SVO_SERPENTINE ? (int)(b.launches++ & 1u) : 0;
@@ -1147,6 +1418,12 @@ inline int persist_launch(PersistBuffers &b, const uint8_t *pool, const Frame &f
   }
   if ((e = hipEventRecord(b.head_done[hset], stream)) != hipSuccess) return (int)e;
   b.head_used[hset] = true;
+  if (a.kept && a.kept_fill) {
+    if ((e = hipEventRecord(b.kept_filled, stream)) != hipSuccess) return (int)e;
+    b.kept_valid = true; b.kept_fill_inflight = true; b.kept_fills++;
+  } else if (a.kept) {
+    b.kept_reader[hset] = true; b.kept_reuses++;
+  }
   if (resolve) {
     if (sequence) {
       hipLaunchKernelGGL(persist_resolve_sequence_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y), dim3(64), 0, stream, f, facc, fold, color);

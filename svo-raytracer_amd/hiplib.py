@@ -22,7 +22,7 @@ EXPORTS = [
     "svo_ring_read_depth", "svo_ring_read_hits", "svo_ring_read_pixel", "svo_ring_bind_slot", "svo_ring_device_ptrs",
     "svo_set_reserved_cus", "svo_pool_commit", "svo_ring_forward_slot", "svo_dev_alloc", "svo_dev_free", "svo_dev_read",
     "svo_ipc_export", "svo_ipc_open", "svo_ipc_close", "svo_set_sequence", "svo_ring_submit_cams",
-    "svo_build_from_heightmap16", "svo_launch_info",
+    "svo_build_from_heightmap16", "svo_launch_info", "svo_set_primary_cache", "svo_primary_cache_info",
     "svo_pool_download_range", "svo_brush_sphere", "svo_brush_box", "svo_brush_info", "svo_group_brush_sphere", "svo_group_brush_box",
     "svo_pool_compact", "svo_compact_info", "svo_group_pool_compact",
     "svo_group_create", "svo_group_destroy", "svo_group_last_error", "svo_group_size", "svo_group_member", "svo_group_pool_upload",
@@ -124,6 +124,8 @@ def lib(path=None):
         L.svo_ring_device_ptrs.argtypes = [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                            ctypes.POINTER(u64), ctypes.POINTER(vp)]
         L.svo_set_derived.argtypes = [vp, ci]
+        L.svo_set_primary_cache.argtypes = [vp, ci]
+        L.svo_primary_cache_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci)]
         L.svo_derived_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci), fp]
         L.svo_derived_read.argtypes = [vp, u64, u64, vp, vp]
         L.svo_derived_refresh_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), fp]
@@ -499,6 +501,16 @@ class HipContext:
         w, p, t = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         self._chk(self._L.svo_launch_info(self._h, ctypes.byref(w), ctypes.byref(p), ctypes.byref(t)))
         return {"waves": w.value, "waves_per_cu": p.value, "round_threshold_sixteenths": t.value}
+
+    def set_primary_cache(self, enabled):
+        """the primary-hit cache of a still camera (default on): off = every submission casts its primary rays"""
+        self._chk(self._L.svo_set_primary_cache(self._h, 1 if enabled else 0))
+
+    def primary_cache_info(self):
+        """launches that wrote / read the cache, the device memory it holds, and its state (0 empty, 1 filling, 2 ready)"""
+        f, r, b, s = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
+        self._chk(self._L.svo_primary_cache_info(self._h, ctypes.byref(f), ctypes.byref(r), ctypes.byref(b), ctypes.byref(s)))
+        return {"fills": int(f.value), "reuses": int(r.value), "bytes": int(b.value), "state": int(s.value)}
 
     def set_derived(self, mode):
         """0 = walk the pool's records as the shader does, 1 (default) = walk the interior-descriptor table when the

@@ -171,7 +171,9 @@ int svo_set_pipeline(svo_ctx *ctx, int pipeline);
  * call.  A positive value is used as given everywhere (a caller that alternates its own streams with svo_set_stream: ~10).
  * The threshold 9 is the optimum of the bench scenes (8: -0.6 % on the default cell, -1.4 % on the worst terrain cell); scenes
  * whose rays take hundreds of iterations -- the "dust" cells of profiles/round6_matrix.md -- prefer 8 by 1.4 ... 3.5 %
- * (profiles/round6_sweep_hostile_cell.md): a host that renders such scenes calls svo_set_tuning(ctx, 0, 8). */
+ * (profiles/round6_sweep_hostile_cell.md): a host that renders such scenes calls svo_set_tuning(ctx, 0, 8).  The threshold
+ * goes from 1 to 16; 16 = a round behind every trip (no lane ever waits for another: the most rounds there can be, a test
+ * setting).  The shape and the threshold also size svo_cast_rays. */
 int svo_set_tuning(svo_ctx *ctx, int waves_per_cu, int round_threshold_sixteenths);
 /* shape of the last pipeline-1 launch of the context: persistent waves launched, waves per CU they were sized by, round
  * threshold in sixteenths (any pointer may be NULL).  Diagnostic: what svo_set_tuning's automatic choice resolved to. */
@@ -292,6 +294,41 @@ int svo_pool_compact(svo_ctx *ctx, uint64_t *old_nbytes, uint64_t *new_nbytes);
 /* what compaction did: *calls that succeeded so far, and of the last one the *records copied (the root included), the
  * *levels of block-owning nodes and the GPU time of planning and writing.  Any may be NULL. */
 int svo_compact_info(svo_ctx *ctx, uint64_t *calls, uint64_t *records, int *levels, float *gpu_ms);
+
+/* ---- ray queries ---------------------------------------------------------------------- */
+/* replaces, for a host that edits: Camera.getRayPickLocation (one depth at one pixel of the last frame) and the crosshair
+ * read-back Main.placeSDF's position comes from (Main.java:132-146, 338-353) -- where a brush lands away from the crosshair,
+ * what lies under the mouse, line of sight, the ground under a point, collision sweeps: rays of the host's own, many per
+ * tick, without rendering a frame.
+ * A ray is six floats {ox, oy, oz, dx, dy, dz} in the shader's space (the octree is the cube [1, 2]^3, as for
+ * svo_set_camera).  Ray k is cast exactly as svotrace.comp:main casts the primary ray of a camera at o: d = normalize(dir),
+ * intersectOctree(o, d, ..., MAX_DEPTH, coneTrace = false) from t = 0, and hits[k] is the svo_hit a frame writes for a
+ * pixel's first cast: pointer / raw_normal / value / level / iter / t; a miss has pointer 0, t = 0 and keeps iter; an
+ * all-NaN ray reports iter = 1501.  Output order is input order.  The bytes are the same over the descriptor table and
+ * over the pool's records (svo_set_derived), and in every build of the library.
+ * The kernel (svo_rays.hip.h) is pipeline 1's persistent waves with lanes that draw ray indices instead of pixels:
+ * min(ceil(n / 64), waves per CU x CUs) waves -- waves per CU from svo_set_tuning when positive, else what a waiting
+ * dispatch uses -- and svo_set_tuning's round threshold.  Like a dispatch, a call builds the descriptor table first if the
+ * pool changed, and walks the records when the pool is not derivable or the mode is 0.
+ * rays / hits: host memory; the call copies the rays in, runs on the context's current stream, waits and copies the
+ * records out (staging buffers of the library's own, grown as needed, freed by svo_destroy).
+ * n = 0: SVO_OK, nothing is launched and nothing counted (svo_cast_info's calls are launches).  SVO_E_TOOLARGE above 2^26
+ * rays (checked first, before any allocation), SVO_E_INVALID for a NULL pointer with n > 0, SVO_E_NOPOOL before a pool
+ * exists; nothing of the context changes on failure.  A call touches none of: camera, params, images, ring, pick,
+ * primary-hit cache, svo_stats.  Pool mutators wait for the whole device, so a cast in flight sees the pool before or
+ * after an edit, never torn.
+ * Deliberately not here: cone rays; a per-ray t_max or an any-hit early-out (either changes iter and needs a parity
+ * statement of its own); a hit position or a decoded normal in the record (the position is o + t d, the normal is
+ * raw_normal); the N-GPU group (its member 0's context serves: svo_group_member). */
+int svo_cast_rays(svo_ctx *ctx, const float *rays, uint32_t n, svo_hit *hits);
+/* the same with both arrays in device memory on the context's GPU (e.g. torch tensors): only enqueues on the context's
+ * current stream (svo_set_stream is honoured) and returns; svo_sync or the caller's own stream ordering applies.  The
+ * arrays must stay alive and untouched until the cast has completed. */
+int svo_cast_rays_device(svo_ctx *ctx, const void *d_rays, uint32_t n, void *d_hits);
+/* *calls / *rays: casts launched and rays cast since the context was made; of the last call the persistent *waves launched,
+ * the *walk used (1 = descriptor table, 0 = records) and its GPU time (HIP events around it on its stream; 0 until the call
+ * has completed -- this function never waits).  Any may be NULL. */
+int svo_cast_info(svo_ctx *ctx, uint64_t *calls, uint64_t *rays, int *waves, int *walk, float *gpu_ms);
 
 /* record per-pixel svo_hit (costs 16 B/pixel of stores); default on */
 int svo_set_hit_records(svo_ctx *ctx, int enabled);

@@ -50,6 +50,13 @@ jint Java_src_engine_HipRenderer_nPoolCompact(void *env, void *cls, jlong ctx, j
 /* svo_compact_info: returns the calls made so far (or a negative status); counts_addr: 2 longs {records copied, levels} of
  * the last one, ms_addr: 1 float (its GPU time); 0 = not wanted */
 jlong Java_src_engine_HipRenderer_nCompactInfo(void *env, void *cls, jlong ctx, jlong counts_addr, jlong ms_addr);
+/* svo_cast_rays: n rays of six floats at rays_addr (host memory, e.g. a direct FloatBuffer), n 16-byte svo_hit records to
+ * hits_addr, in input order; waits for the cast */
+jint Java_src_engine_HipRenderer_nCastRays(void *env, void *cls, jlong ctx, jlong rays_addr, jint n, jlong hits_addr);
+/* svo_cast_info: returns the casts launched so far (or a negative status); counts_addr: 3 longs {rays cast so far, persistent
+ * waves of the last call, its walk: 1 = descriptor table, 0 = records}, ms_addr: 1 float (its GPU time, 0 until it has
+ * completed); 0 = not wanted */
+jlong Java_src_engine_HipRenderer_nCastInfo(void *env, void *cls, jlong ctx, jlong counts_addr, jlong ms_addr);
 /* svo_group_pool_compact: every member's replica */
 jint Java_src_engine_HipRenderer_nGroupPoolCompact(void *env, void *cls, jlong g, jlong sizes_addr);
 /* the stroke on every member's replica (svo_group_brush_*) */

@@ -211,6 +211,29 @@ public class HipRenderer {
     return out;
   }
 
+  /**
+   * svo_cast_rays: the host's own rays through the octree, without a frame -- what Camera.getRayPickLocation (one depth at
+   * one pixel of the last frame) and the crosshair read-back in front of Main.placeSDF cannot give.  `rays`: direct buffer,
+   * six floats {ox, oy, oz, dx, dy, dz} per ray from its position on, in the shader's space (the octree is [1, 2]^3);
+   * `hits`: direct buffer with room for 16 bytes per ray from its position on -- svo_hit {int pointer (0 = miss), short
+   * rawNormal, byte value, byte level, int iter, float t} in native byte order, ray k at byte 16 k.  Waits for the cast.
+   */
+  public void castRays(java.nio.FloatBuffer rays, ByteBuffer hits) {
+    int n = rays.remaining() / 6;
+    if (hits.remaining() < 16L * n)
+      throw new IllegalArgumentException("castRays: 16 bytes of hit record per ray");
+    check(nCastRays(ctx, MemoryUtil.memAddress(rays), n, MemoryUtil.memAddress(hits)));
+  }
+
+  /** svo_cast_info: {casts launched so far, rays cast so far, persistent waves of the last call, its walk (1 = table)}. */
+  public long[] castInfo() {
+    ByteBuffer counts = MemoryUtil.memAlloc(24);
+    long calls = nCastInfo(ctx, MemoryUtil.memAddress(counts), 0L);
+    long[] out = {calls, counts.getLong(0), counts.getLong(8), counts.getLong(16)};
+    MemoryUtil.memFree(counts);
+    return out;
+  }
+
   public Shader getShaderByName(String name) {
     for (Shader shader : shaders) {
       if (shader.name.equals(name))
@@ -743,6 +766,8 @@ public class HipRenderer {
   private static native int nPoolCompact(long ctx, long sizesAddr);
   private static native long nCompactInfo(long ctx, long countsAddr, long msAddr);
   private static native int nGroupPoolCompact(long g, long sizesAddr);
+  private static native int nCastRays(long ctx, long raysAddr, int n, long hitsAddr);
+  private static native long nCastInfo(long ctx, long countsAddr, long msAddr);
   private static native int nSetCamera(long ctx, float px, float py, float pz, float l1x, float l1y, float l1z,
       float l2x, float l2y, float l2z, float r1x, float r1y, float r1z, float r2x, float r2y, float r2z);
   private static native int nSetParams(long ctx, int frameNumber, int renderMode, int bufferEnd, int useBeam,

@@ -33,6 +33,7 @@
 #include "svo_derive.hip.h"
 #include "svo_brush.hip.h"
 #include "svo_compact.hip.h"
+#include "svo_rays.hip.h"
 
 using namespace svo;
 
@@ -118,6 +119,7 @@ struct svo_ctx {
   PersistBuffers pb;
   brush::State bs;             // work items and counters of svo_brush_* (made at the first stroke), what the last stroke did
   compact::State cs;           // events of svo_pool_compact (made at the first call), what the last call did
+  rays::State rs;              // counters, staging buffers and counts of svo_cast_rays* (made at the first call)
   // frames in flight behind the boundary (svo_ring_*): per slot a stream of its own, output buffers for up to
   // ring_frames consecutive frames, and the events around its last submission
   struct RingSlot : Planes {        // (the planes: library-owned images, frame after frame)
@@ -297,6 +299,7 @@ int svo_destroy(svo_ctx *c) {
   derive::free_table(c->dt);
   brush::free_state(c->bs);
   compact::free_state(c->cs);
+  rays::free_state(c->rs);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   ring_free(c);
@@ -765,7 +768,8 @@ int svo_set_pipeline(svo_ctx *c, int pipeline) {
 }
 
 int svo_set_tuning(svo_ctx *c, int waves_per_cu, int round_threshold_sixteenths) {
-  if (!c || waves_per_cu < 0 || round_threshold_sixteenths < 0 || round_threshold_sixteenths > 15)
+  // (16: every burst is one trip -- a round behind every stop, and behind every trip without one: the most rounds there can be)
+  if (!c || waves_per_cu < 0 || round_threshold_sixteenths < 0 || round_threshold_sixteenths > 16)
     return fail(c, SVO_E_INVALID, "svo_set_tuning: bad values");
   c->pb.waves_per_cu = waves_per_cu;
   c->pb.thresh_num = round_threshold_sixteenths;   // 0 = the running kernel's own default
@@ -1282,6 +1286,83 @@ int svo_time_frames(svo_ctx *c, int warmup, int iters, float *ms) {
   return SVO_OK;
 }
 
+
+// ---------------------------------------------------------------- ray queries (svo_rays.hip.h)
+// the checks both variants share; n > 0 behind it
+static int cast_check(svo_ctx *c, const void *rays_, uint32_t n, const void *hits, const char *who) {
+  if (n > rays::kMaxRays) return fail(c, SVO_E_TOOLARGE, std::string(who) + ": at most 2^26 rays per call");
+  if (!rays_ || !hits) return fail(c, SVO_E_INVALID, std::string(who) + ": null buffer");
+  if (!c->d_pool || c->pool_len < 7) return fail(c, SVO_E_NOPOOL, std::string(who) + ": no pool uploaded");
+  return SVO_OK;
+}
+
+// enqueues the cast of n > 0 rays in device memory on the context's current stream
+static int cast_enqueue(svo_ctx *c, const void *d_rays, uint32_t n, void *d_hits, const char *who) {
+#if SVO_VARIANTS
+  static const int env_mode = getenv("SVO_DERIVED") ? atoi(getenv("SVO_DERIVED")) : -1;   // A/B override, as for a dispatch
+#else
+  const int env_mode = -1;
+#endif
+  const int mode = env_mode >= 0 ? env_mode : c->derived_mode;
+  int rc;
+  if (mode != 0 && (rc = ensure_derived(c)) != SVO_OK) return rc;
+  const bool walk_table = mode != 0 && c->dt.ok;   // not derivable: the records are walked
+  hipError_t e = rays::prepare(c->rs);
+  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  rays::Args a{};
+  a.pool = c->d_pool; a.pool_len = (uint32_t)c->pool_len;
+  a.desc = walk_table ? c->dt.desc : nullptr; a.aux = walk_table ? c->dt.aux : nullptr; a.desc_count = walk_table ? c->dt.count : 0u;
+  a.ntab = c->pb.ntab;
+  a.rays = (const float *)d_rays; a.hits = (uint4 *)d_hits; a.n = n;
+  a.thresh_num = c->pb.thresh_num > 0 ? c->pb.thresh_num : 9;
+  e = rays::launch(c->rs, a, walk_table, c->pb.waves_per_cu, c->stream);
+  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return SVO_OK;
+}
+
+int svo_cast_rays_device(svo_ctx *c, const void *d_rays, uint32_t n, void *d_hits) {
+  if (!c) return SVO_E_INVALID;
+  if (n == 0) return SVO_OK;
+  int rc = cast_check(c, d_rays, n, d_hits, "svo_cast_rays_device");
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return cast_enqueue(c, d_rays, n, d_hits, "svo_cast_rays_device");
+}
+
+int svo_cast_rays(svo_ctx *c, const float *rays_, uint32_t n, svo_hit *hits) {
+  if (!c) return SVO_E_INVALID;
+  if (n == 0) return SVO_OK;
+  int rc = cast_check(c, rays_, n, hits, "svo_cast_rays");
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  rays::State &s = c->rs;
+  if (s.cap < n) {
+    // (the staging buffers are idle between calls: every call that used them has waited for its cast before it returned)
+    float *nr = nullptr; uint4 *nh = nullptr;
+    hipError_t e = hipMalloc((void **)&nr, (size_t)n * 6 * sizeof(float));
+    if (e == hipSuccess && (e = hipMalloc((void **)&nh, (size_t)n * sizeof(uint4))) != hipSuccess) (void)hipFree(nr);
+    if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string("svo_cast_rays: staging buffers: ") + hipGetErrorString(e));
+    if (s.d_rays) (void)hipFree(s.d_rays);
+    if (s.d_hits) (void)hipFree(s.d_hits);
+    s.d_rays = nr; s.d_hits = nh; s.cap = n;
+  }
+  HIPCHK(c, hipMemcpyAsync(s.d_rays, rays_, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  rc = cast_enqueue(c, s.d_rays, n, s.d_hits, "svo_cast_rays");
+  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }   // (the copy in may still read the caller's rays)
+  HIPCHK(c, hipMemcpyAsync(hits, s.d_hits, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SVO_OK;
+}
+
+int svo_cast_info(svo_ctx *c, uint64_t *calls, uint64_t *rays_, int *waves, int *walk, float *gpu_ms) {
+  if (!c) return SVO_E_INVALID;
+  if (calls) *calls = c->rs.calls;
+  if (rays_) *rays_ = c->rs.rays;
+  if (waves) *waves = c->rs.waves;
+  if (walk) *walk = c->rs.walk;
+  if (gpu_ms) { HIPCHK(c, hipSetDevice(c->device)); *gpu_ms = rays::last_ms(c->rs); }
+  return SVO_OK;
+}
 
 // ---------------------------------------------------------------- frames in flight behind the boundary
 static int ring_create_impl(svo_ctx *c, int slots, int frames_per_slot, int want_hits, bool own_images);

@@ -58,6 +58,21 @@ jlong Java_src_engine_HipRenderer_nCompactInfo(void *, void *, jlong ctx, jlong 
   if (counts_addr) { ((jlong *)(intptr_t)counts_addr)[0] = (jlong)records; ((jlong *)(intptr_t)counts_addr)[1] = (jlong)levels; }
   return (jlong)calls;
 }
+jint Java_src_engine_HipRenderer_nCastRays(void *, void *, jlong ctx, jlong rays_addr, jint n, jlong hits_addr) {
+  if (n < 0) return SVO_E_INVALID;
+  return svo_cast_rays((svo_ctx *)(intptr_t)ctx, (const float *)(intptr_t)rays_addr, (uint32_t)n, (svo_hit *)(intptr_t)hits_addr);
+}
+jlong Java_src_engine_HipRenderer_nCastInfo(void *, void *, jlong ctx, jlong counts_addr, jlong ms_addr) {
+  uint64_t calls = 0, nrays = 0;
+  int waves = 0, walk = 0;
+  const int rc = svo_cast_info((svo_ctx *)(intptr_t)ctx, &calls, &nrays, &waves, &walk, (float *)(intptr_t)ms_addr);
+  if (rc != SVO_OK) return (jlong)rc;
+  if (counts_addr) {
+    jlong *v = (jlong *)(intptr_t)counts_addr;
+    v[0] = (jlong)nrays; v[1] = (jlong)waves; v[2] = (jlong)walk;
+  }
+  return (jlong)calls;
+}
 jint Java_src_engine_HipRenderer_nSetCamera(void *, void *, jlong ctx, jfloat px, jfloat py, jfloat pz, jfloat l1x,
                                             jfloat l1y, jfloat l1z, jfloat l2x, jfloat l2y, jfloat l2z, jfloat r1x,
                                             jfloat r1y, jfloat r1z, jfloat r2x, jfloat r2y, jfloat r2z) {

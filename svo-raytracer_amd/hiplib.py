@@ -25,6 +25,7 @@ EXPORTS = [
     "svo_build_from_heightmap16", "svo_launch_info", "svo_set_primary_cache", "svo_primary_cache_info",
     "svo_pool_download_range", "svo_brush_sphere", "svo_brush_box", "svo_brush_info", "svo_group_brush_sphere", "svo_group_brush_box",
     "svo_pool_compact", "svo_compact_info", "svo_group_pool_compact",
+    "svo_cast_rays", "svo_cast_rays_device", "svo_cast_info",
     "svo_group_create", "svo_group_destroy", "svo_group_last_error", "svo_group_size", "svo_group_member", "svo_group_pool_upload",
     "svo_group_pool_update", "svo_group_pool_download", "svo_group_build_from_heightmap", "svo_group_set_camera",
     "svo_group_set_params", "svo_group_set_pipeline", "svo_group_set_tuning", "svo_group_set_progressive", "svo_group_set_sequence",
@@ -82,6 +83,9 @@ def lib(path=None):
         L.svo_pool_compact.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
         L.svo_compact_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci), fp]
         L.svo_group_pool_compact.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.svo_cast_rays.argtypes = [vp, vp, ctypes.c_uint32, vp]
+        L.svo_cast_rays_device.argtypes = [vp, vp, ctypes.c_uint32, vp]
+        L.svo_cast_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci), ctypes.POINTER(ci), fp]
         L.svo_pool_reserve.argtypes = [vp, u64]
         L.svo_pool_upload_device.argtypes = [vp, vp, u64]
         L.svo_build_from_heightmap.argtypes = [vp, vp, vp, ci, ctypes.POINTER(u64)]
@@ -421,6 +425,28 @@ class HipContext:
         calls, records, levels, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int(), ctypes.c_float()
         self._chk(self._L.svo_compact_info(self._h, ctypes.byref(calls), ctypes.byref(records), ctypes.byref(levels), ctypes.byref(ms)))
         return {"calls": int(calls.value), "records": int(records.value), "levels": int(levels.value), "gpu_ms": float(ms.value)}
+
+    def cast_rays(self, rays):
+        """svo_cast_rays: `rays` (n, 6) float32 {ox, oy, oz, dx, dy, dz} in the shader's space, each cast as a primary ray;
+        returns n HIT_DTYPE records in input order (a miss: pointer 0, t 0, iter kept).  Waits for the cast."""
+        rays = np.ascontiguousarray(np.asarray(rays, dtype=np.float32).reshape(-1, 6))
+        hits = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        self._chk(self._L.svo_cast_rays(self._h, rays.ctypes.data, rays.shape[0], hits.ctypes.data))
+        return hits
+
+    def cast_rays_device(self, rays_ptr, n, hits_ptr):
+        """svo_cast_rays_device: n rays (6 float32 each) and n 16-byte records in device memory on the context's GPU; only
+        enqueues on the context's current stream (set_stream)"""
+        self._chk(self._L.svo_cast_rays_device(self._h, ctypes.c_void_p(rays_ptr or 0), int(n), ctypes.c_void_p(hits_ptr or 0)))
+
+    def cast_info(self):
+        """svo_cast_info: casts launched and rays cast so far; of the last call the persistent waves, the walk (1 = descriptor
+        table, 0 = records) and the GPU time (0 until it has completed; never waits)"""
+        calls, rays, waves, walk, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+        self._chk(self._L.svo_cast_info(self._h, ctypes.byref(calls), ctypes.byref(rays), ctypes.byref(waves), ctypes.byref(walk),
+                                        ctypes.byref(ms)))
+        return {"calls": int(calls.value), "rays": int(rays.value), "waves": int(waves.value), "walk": int(walk.value),
+                "gpu_ms": float(ms.value)}
 
     def pool_upload_device(self, dptr, nbytes):
         self._chk(self._L.svo_pool_upload_device(self._h, ctypes.c_void_p(int(dptr)), int(nbytes)))

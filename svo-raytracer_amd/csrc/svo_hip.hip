@@ -116,7 +116,7 @@ struct svo_ctx {
 #if SVO_VARIANTS
   WavefrontBuffers wf;
 #endif
-  PersistBuffers pb;
+  PersistState pb;            // the persistent pipeline: settings (they outlive svo_resize), device limits, per-size buffers
   brush::State bs;             // work items and counters of svo_brush_* (made at the first stroke), what the last stroke did
   compact::State cs;           // events of svo_pool_compact (made at the first call), what the last call did
   rays::State rs;              // counters, staging buffers and counts of svo_cast_rays* (made at the first call)
@@ -173,7 +173,7 @@ struct Target {
   float cam[15] = {};
   const FrameVar *cams = nullptr;         // per-frame cameras / frame numbers of the batch (svo_ring_submit_cams), on the host, ...
   svo_ctx::RingSlot *cams_slot = nullptr; // ... and the slot that keeps them on the device (d_fvar) and stages the copy (ring_copy_cams)
-  enum Shape { kPlain, kRing, kOverlap } shape = kPlain;   // the persistent launch's shape unless svo_set_tuning named one
+  LaunchShape shape = kPlain;                              // the persistent launch's shape unless svo_set_tuning named one
   int overlap_sets = 0;                                    // kOverlap: the number of sets taking turns
 };
 
@@ -209,7 +209,7 @@ static hipError_t alloc_planes(size_t n_elems, bool want_hits, Planes &out) {
 static void pool_changed(svo_ctx *c) {
   if (c) {
     c->beam_live_valid = false; c->derived_valid = false;
-    c->pb.pool_epoch++; persist_kept_drop(c->pb);   // the primary-hit cache: part of its key, and empty from here on
+    c->pb.set.pool_epoch++; persist_kept_drop(c->pb.buf);   // the primary-hit cache: part of its key, and empty from here on
   }
 }
 
@@ -246,7 +246,6 @@ int svo_create(int device, svo_ctx **out) {
     hipLaunchKernelGGL(normal_table_kernel, dim3(256), dim3(256), 0, c->sets[0].stream, c->d_ntab);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->sets[0].stream) != hipSuccess) { (void)hipFree(c->d_ntab); c->d_ntab = nullptr; }
   }
-  c->pb.ntab = c->d_ntab;   // (null: the kernels decode in place)
   *out = c;
   return SVO_OK;
 }
@@ -264,7 +263,7 @@ static void ring_free(svo_ctx *c) {
     if (s.stream) (void)hipStreamDestroy(s.stream);
   }
   c->ring.clear();
-  c->pb.cus_reserved = 0;
+  c->pb.set.cus_reserved = 0;
   c->ring_frames = 0; c->ring_stride = 0; c->ring_next = 0;
 }
 
@@ -277,7 +276,7 @@ static void free_outputs(svo_ctx *c) {
 #if SVO_VARIANTS
   wavefront_free(c->wf);
 #endif
-  persist_free(c->pb);
+  persist_free(c->pb.buf);
   for (int i = 0; i < svo_ctx::kBeamSets; i++) {
     if (c->d_beam[i]) (void)hipFree(c->d_beam[i]);
     c->d_beam[i] = nullptr;
@@ -771,8 +770,8 @@ int svo_set_tuning(svo_ctx *c, int waves_per_cu, int round_threshold_sixteenths)
   // (16: every burst is one trip -- a round behind every stop, and behind every trip without one: the most rounds there can be)
   if (!c || waves_per_cu < 0 || round_threshold_sixteenths < 0 || round_threshold_sixteenths > 16)
     return fail(c, SVO_E_INVALID, "svo_set_tuning: bad values");
-  c->pb.waves_per_cu = waves_per_cu;
-  c->pb.thresh_num = round_threshold_sixteenths;   // 0 = the running kernel's own default
+  c->pb.set.waves_per_cu = waves_per_cu;
+  c->pb.set.thresh_num = round_threshold_sixteenths;   // 0 = the running kernel's own default
 #if SVO_VARIANTS
   c->wf.waves_per_cu = waves_per_cu;
   c->wf.thresh_num = round_threshold_sixteenths ? round_threshold_sixteenths : 12;
@@ -782,26 +781,26 @@ int svo_set_tuning(svo_ctx *c, int waves_per_cu, int round_threshold_sixteenths)
 
 int svo_launch_info(svo_ctx *c, int *waves, int *waves_per_cu, int *round_threshold_sixteenths) {
   if (!c) return SVO_E_INVALID;
-  if (waves) *waves = c->pb.last_blocks;
-  if (waves_per_cu) *waves_per_cu = c->pb.last_per_cu;
-  if (round_threshold_sixteenths) *round_threshold_sixteenths = c->pb.last_thresh;
+  if (waves) *waves = c->pb.buf.last_blocks;
+  if (waves_per_cu) *waves_per_cu = c->pb.buf.last_per_cu;
+  if (round_threshold_sixteenths) *round_threshold_sixteenths = c->pb.buf.last_thresh;
   return SVO_OK;
 }
 
 int svo_set_primary_cache(svo_ctx *c, int enabled) {
   if (!c) return SVO_E_INVALID;
-  c->pb.kept_mode = enabled != 0 ? 1 : 0;
-  if (!enabled) persist_kept_drop(c->pb);
+  c->pb.set.kept_mode = enabled != 0 ? 1 : 0;
+  if (!enabled) persist_kept_drop(c->pb.buf);
   return SVO_OK;
 }
 
 int svo_primary_cache_info(svo_ctx *c, uint64_t *fills, uint64_t *reuses, uint64_t *bytes, int *state) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  if (fills) *fills = c->pb.kept_fills;
-  if (reuses) *reuses = c->pb.kept_reuses;
-  if (bytes) *bytes = (uint64_t)c->pb.kept_cap * 3 * sizeof(uint4);
-  if (state) *state = !c->pb.kept_valid ? 0 : (persist_kept_filled(c->pb) ? 2 : 1);
+  if (fills) *fills = c->pb.set.kept_fills;
+  if (reuses) *reuses = c->pb.set.kept_reuses;
+  if (bytes) *bytes = (uint64_t)c->pb.buf.kept_cap * 3 * sizeof(uint4);
+  if (state) *state = !c->pb.buf.kept_valid ? 0 : (persist_kept_filled(c->pb.buf) ? 2 : 1);
   return SVO_OK;
 }
 
@@ -978,15 +977,8 @@ static int launch_beam(svo_ctx *c, const Target &t, Frame &f, int &set) {
   const int bw = (f.width + kBeamBlock - 1) / kBeamBlock, bh = (f.height + kBeamBlock - 1) / kBeamBlock;
   const size_t need = (size_t)bw * (size_t)bh;
   if (c->beam_cap < need) {
-    HIPCHK(c, hipDeviceSynchronize());
-    for (int i = 0; i < svo_ctx::kBeamSets; i++) {
-      if (c->d_beam[i]) (void)hipFree(c->d_beam[i]);
-      c->d_beam[i] = nullptr;
-      c->beam_used[i] = false;
-      HIPCHK(c, hipMalloc((void **)&c->d_beam[i], need * sizeof(float)));
-      if (!c->beam_done[i]) HIPCHK(c, hipEventCreateWithFlags(&c->beam_done[i], hipEventDisableTiming));
-    }
-    c->beam_cap = need;
+    HIPCHK(c, grow_device_buffers(c->d_beam, c->beam_used, c->beam_cap, need, need * sizeof(float)));
+    for (auto &ev : c->beam_done) if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   }
   if (!c->beam_live_valid) {
     // once per pool: mark the live nodes of the top levels, bottom-up.  The pool only changes while the device is idle
@@ -1027,6 +1019,23 @@ static int ensure_derived(svo_ctx *c) {
   return SVO_OK;
 }
 
+// Which octree a cast reads: the descriptor table when the context asks for it (derived_mode; a variants build's SVO_DERIVED
+// overrides, for A/B runs) and the pool is derivable -- not deeper than 13 levels, not cyclic -- else the records.  The table is
+// brought up to date here.
+static int pick_walk(svo_ctx *c, bool &walk_table) {
+#if SVO_VARIANTS
+  static const int env_mode = getenv("SVO_DERIVED") ? atoi(getenv("SVO_DERIVED")) : -1;
+#else
+  const int env_mode = -1;
+#endif
+  const int mode = env_mode >= 0 ? env_mode : c->derived_mode;
+  walk_table = false;
+  if (mode == 0) return SVO_OK;
+  const int rc = ensure_derived(c);
+  walk_table = rc == SVO_OK && c->dt.ok;
+  return rc;
+}
+
 static int launch_frame(svo_ctx *c, const Target &t, bool count) {
   Frame f;
   int rc = make_frame(c, t, f);
@@ -1058,7 +1067,7 @@ static int launch_frame(svo_ctx *c, const Target &t, bool count) {
     if (c->seq_fresh && writes_rows)
       HIPCHK(c, hipMemsetAsync(o.color + (size_t)f.out_y0 * (size_t)f.width, 0, (size_t)(last_row - f.out_y0) * (size_t)f.width * 4, t.stream));
     Frame probe = f;
-    if (c->pipeline == 1 && f.spp <= 1 && persist_can_fold(probe, c->seq)) {
+    if (c->pipeline == 1 && f.spp <= 1 && persist_can_fold(probe, c->seq, persist_fold_budget())) {
       // the persistent pipeline carries the whole sequence in one launch and blends it in frame order afterwards
       f.seq = c->seq;
       rc = launch_frame_kernels(c, t, f, count, o.color, o.depth, o.hits);
@@ -1096,21 +1105,16 @@ static int launch_frame_kernels(svo_ctx *c, const Target &t, Frame &f, bool coun
   int rc = SVO_OK;
   if (count) HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(DeviceCounters), t.stream));
   if (c->pipeline == 1 && !count) {
-#if SVO_VARIANTS
-    static const int env_mode = getenv("SVO_DERIVED") ? atoi(getenv("SVO_DERIVED")) : -1;   // A/B override
-#else
-    const int env_mode = -1;
-#endif
-    const int mode = env_mode >= 0 ? env_mode : c->derived_mode;
-    if (mode != 0 && (rc = ensure_derived(c)) != SVO_OK) return rc;
-    const bool walk_table = mode != 0 && c->dt.ok;   // not derivable (deeper than 13 levels, cyclic): the records are walked
-    // the target's launch-shape hint reaches persist_launch through these three, set for the one call
-    c->pb.in_ring = t.shape == Target::kRing; c->pb.in_overlap = t.shape == Target::kOverlap;
-    if (c->pb.in_overlap) c->pb.overlap_sets = t.overlap_sets;
-    rc = persist_launch(c->pb, c->d_pool, f, color, depth, hits, out_elems(c, f), t.stream, walk_table ? c->dt.desc : nullptr,
-                        walk_table ? c->dt.aux : nullptr, walk_table ? c->dt.count : 0u, t.cams ? t.cams_slot->d_fvar : nullptr,
-                        t.cams, ring_copy_cams, (void *)&t);
-    c->pb.in_ring = false; c->pb.in_overlap = false;
+    bool walk_table;
+    if ((rc = pick_walk(c, walk_table)) != SVO_OK) return rc;
+    PersistLaunch in;
+    in.pool = c->d_pool; in.color = color; in.depth = depth; in.hits = hits; in.out_npix = out_elems(c, f); in.stream = t.stream;
+    in.shape = t.shape; in.overlap_sets = t.overlap_sets;
+    if (walk_table) { in.desc = c->dt.desc; in.aux = c->dt.aux; in.desc_count = c->dt.count; }
+    in.ntab = c->d_ntab;
+    if (t.cams) in.fvar = t.cams_slot->d_fvar;
+    in.fvar_host = t.cams; in.copy_cams = ring_copy_cams; in.copy_arg = (void *)&t;
+    rc = persist_launch(c->pb, f, in);
     if (rc) return fail(c, SVO_E_HIP, std::string("persistent pipeline: ") + hipGetErrorString((hipError_t)rc));
     return SVO_OK;
   }
@@ -1199,7 +1203,7 @@ int svo_dispatch_async(svo_ctx *c) {
     c->others_inflight = true;
   }
   Target t = current_target(c);
-  if (overlapped) { t.shape = Target::kOverlap; t.overlap_sets = c->overlap; }   // the launch shape of overlapping one-frame launches
+  if (overlapped) { t.shape = kOverlap; t.overlap_sets = c->overlap; }   // the launch shape of overlapping one-frame launches
   int rc = launch_pick(c, t);
   if (rc == SVO_OK) {
     rc = launch_frame(c, t, false);
@@ -1298,24 +1302,18 @@ static int cast_check(svo_ctx *c, const void *rays_, uint32_t n, const void *hit
 
 // enqueues the cast of n > 0 rays in device memory on the context's current stream
 static int cast_enqueue(svo_ctx *c, const void *d_rays, uint32_t n, void *d_hits, const char *who) {
-#if SVO_VARIANTS
-  static const int env_mode = getenv("SVO_DERIVED") ? atoi(getenv("SVO_DERIVED")) : -1;   // A/B override, as for a dispatch
-#else
-  const int env_mode = -1;
-#endif
-  const int mode = env_mode >= 0 ? env_mode : c->derived_mode;
-  int rc;
-  if (mode != 0 && (rc = ensure_derived(c)) != SVO_OK) return rc;
-  const bool walk_table = mode != 0 && c->dt.ok;   // not derivable: the records are walked
+  bool walk_table;
+  const int rc = pick_walk(c, walk_table);
+  if (rc) return rc;
   hipError_t e = rays::prepare(c->rs);
   if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
   rays::Args a{};
   a.pool = c->d_pool; a.pool_len = (uint32_t)c->pool_len;
   a.desc = walk_table ? c->dt.desc : nullptr; a.aux = walk_table ? c->dt.aux : nullptr; a.desc_count = walk_table ? c->dt.count : 0u;
-  a.ntab = c->pb.ntab;
+  a.ntab = c->d_ntab;
   a.rays = (const float *)d_rays; a.hits = (uint4 *)d_hits; a.n = n;
-  a.thresh_num = c->pb.thresh_num > 0 ? c->pb.thresh_num : 9;
-  e = rays::launch(c->rs, a, walk_table, c->pb.waves_per_cu, c->stream);
+  a.thresh_num = persist_thresh(c->pb.set);
+  e = rays::launch(c->rs, a, walk_table, c->pb.set, c->stream);
   if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
   return SVO_OK;
 }
@@ -1389,7 +1387,7 @@ static int ring_create_impl(svo_ctx *c, int slots, int frames_per_slot, int want
   const int reserve = std::min(c->reserved_cus * 8, ncu - 8);
   for (int b = ncu - reserve; b < ncu && reserve > 0; b++) cumask[(size_t)b >> 5] &= ~(1u << (b & 31));
   if (ncu & 31) cumask.back() &= (1u << (ncu & 31)) - 1u;
-  c->pb.cus_reserved = reserve > 0 ? reserve : 0;
+  c->pb.set.cus_reserved = reserve > 0 ? reserve : 0;
   for (auto &s : c->ring) {
     hipError_t e = reserve > 0 ? hipExtStreamCreateWithCUMask(&s.stream, (uint32_t)cumask.size(), cumask.data())
                                : hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
@@ -1480,7 +1478,7 @@ static int ring_submit(svo_ctx *c, int frame_number, int nframes, const FrameVar
   else { t.out = s; t.frame_stride = c->ring_stride; }
   memcpy(t.cam, c->cam, sizeof t.cam);
   // the launch shape a ring of several slots gets unless svo_set_tuning named one: kRingWavesPerCu persistent waves per CU
-  if (c->ring.size() > 1) t.shape = Target::kRing;
+  if (c->ring.size() > 1) t.shape = kRing;
   int rc = SVO_OK;
   hipError_t e = hipSuccess;
   if (cams && nframes == 1) {           // one frame: simply this frame's camera (beam pre-pass and all)
@@ -1797,10 +1795,10 @@ extern "C" {
 // diagnostic builds only: the diagnostics words of the persistent pipeline's last counter set (16 x u64, then the
 // 64-word histograms of lanes traversing per trip and of lanes in the POP section, 8 x u64 of a round's parts): 704 bytes
 int svo_debug_heads(svo_ctx *c, void *out) {
-  if (!c || !out || !c->pb.heads) return SVO_E_INVALID;
+  if (!c || !out || !c->pb.buf.heads) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipDeviceSynchronize());
-  HIPCHK(c, hipMemcpy(out, c->pb.heads + (size_t)((c->pb.frames - 1) % kHeadSets) * kHeadWords + 8 * kHeadStride, 704, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, c->pb.buf.heads + (size_t)((c->pb.buf.frames - 1) % kHeadSets) * kHeadWords + 8 * kHeadStride, 704, hipMemcpyDeviceToHost));
   return SVO_OK;
 }
 #endif

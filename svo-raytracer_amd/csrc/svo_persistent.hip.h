@@ -21,6 +21,7 @@
 // any pixel.
 #pragma once
 #include "svo_fused.hip.h"
+#include "svo_persist_plan.h"
 #include "svo_trav.h"
 #include "svo_travloop.h"
 #include "svo_travloop2.h"
@@ -51,11 +52,11 @@ struct PersistArgs {
   float *facc;       // spp > 1: colour sums (3 planes of npix)
   size_t npix;
   uint32_t *heads;   // 8 band counters (pixel slots drawn so far)
-  int tiles_per_band;
-  int rows_per_band;   // tile rows per XCD band (SVO_BAND_COLMAJOR)
+  int tiles_per_band;  // unread since the row-major band walk went: kept, because without it hipcc allocates the kernels' registers differently
+  int rows_per_band;   // tile rows per XCD band
   int reverse;         // walk the columns right to left (every other launch)
   int sample;        // sample index of this launch (one launch per sample), 0 when the launch carries all samples
-  int fold;          // samples per pixel carried by this launch (see persist_launch); 1 = one launch per sample
+  int fold;          // samples per pixel carried by this launch (see persist_plan); 1 = one launch per sample
   int group;         // fold > 1: tiles per group of a band's walk (sample by sample inside a group)
   int thresh_num;    // a round starts once active lanes <= thresh_num/16 of those active at its start
   // reciprocals (udiv_magic) of a band's tile rows and of its tile slots per frame, for a full band and for the last one
@@ -74,7 +75,7 @@ struct PersistArgs {
   const float *rc;
   uint32_t rc_stride;
   const float4 *ntab;   // unit normals by 16-bit code (svo_trav2.h), or null
-  // 1 = a band slot is a pixel with all the frames of the batch (persist_span_kernel): chosen once, in persist_launch
+  // 1 = a band slot is a pixel with all the frames of the batch (persist_span_kernel): chosen once, in persist_plan
   int span;
   uint4 *prim;          // ... and the primary-hit records of its lanes, kSpanWords words per persistent lane of the launch
   // the context's primary-hit cache (persist_kept_kernel): three planes of kept_n records, a pixel's at its frame-0 output index
@@ -84,18 +85,10 @@ struct PersistArgs {
   int kept_fill;        // 1 = this launch writes the cache (persist_kept_kernel<true>), 0 = it reads it
 };
 
-// n / d by multiply-high with m = ceil(2^32 / d) = (2^32 + e) / d, 0 <= e < d (made on the host, udiv_magic): with
-// n = q d + r the product is q 2^32 + q e + r (2^32 + e) / d, so the high word is q exactly while e (n + d) < 2^32.
-// The host checks that against the largest n the launch can form (tile slots of a band x frames x samples: a 4K batch of
-// 17 frames, or 1080p with 16 samples x 2 frames, is already past it) and passes m = 0 otherwise = a real division.
+// n / d by multiply-high with the reciprocal m the host made (svo_persist_plan.h::udiv_magic); m = 0: n is past what the
+// reciprocal is exact for = a real division
 __device__ __forceinline__ uint32_t udiv_by(uint32_t n, uint32_t d, uint32_t m) {
   return d <= 1u ? n : (m == 0u ? n / d : __umulhi(n, m));
-}
-inline uint32_t udiv_magic(uint32_t d, uint64_t n_max) {
-  if (d <= 1u) return 0u;
-  const uint32_t m = 0xffffffffu / d + 1u;
-  const uint64_t e = (uint64_t)m * d - (1ull << 32);
-  return e * (n_max + d) < (1ull << 32) ? m : 0u;
 }
 
 __device__ __forceinline__ uint32_t xcc_id() {
@@ -108,10 +101,7 @@ __device__ __forceinline__ uint32_t xcc_id() {
 // its pixels (a.fold > 1), else 0
 __device__ __forceinline__ void persist_emit(const PersistArgs &a, uint32_t pix, uint32_t sk, int px, int py, V3 col, float depth) {
   const uint32_t smp = sk & 0xffffu;
-#ifdef SVO_NO_STORES  // timing experiment only: keep the values alive, skip the stores
-  asm volatile("" ::"v"(col.x), "v"(col.y), "v"(col.z), "v"(depth), "v"(pix));
-  return;
-#endif
+  // (a kernel that stores nothing was a compile-time experiment: the ceiling of any staging scheme, profiles/round4_experiments.txt)
   if (a.f.spp <= 1 && !a.f.progressive) {   // the live shader's case: straight to rgba8
     if (px < 10 && py < 10) col = a.f.dword0 == 0u ? mk(1.f, 0.f, 0.f) : mk(1.f, 1.f, 1.f);
     a.color[pix] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xff000000u;
@@ -216,10 +206,11 @@ struct DescWalk {
   // a new ray starts on a zeroed stack column, like the reference's zero-initialised stack[] (svotrace.comp:227): a pop to a
   // level the ray never pushed then reads {descriptor 0, t_max 0} by itself, and the loop keeps no "pushed" mask
   __device__ __forceinline__ void fresh_stack(Stack &stk, uint32_t lane) const {
-#if SVO_ASM_LOOP && !defined(SVO_TIMING_ONLY_NO_STACK_CLEAR)
+#if SVO_ASM_LOOP
     // (always in the assembly build: trav_loop2's POP reads its entry without a pushed-levels mask.  Round 3's closing
-    // commit lost the define that guarded these stores and shipped a kernel without them; the switch above exists to
-    // price them in an A/B and builds a WRONG kernel; tests/test_kernel_isa.py checks the shipped one.)
+    // commit lost the define that guarded these stores and shipped a kernel without them; tests/test_kernel_isa.py checks
+    // the shipped one.  What the stores cost was priced once with a compile-time switch that built a WRONG kernel:
+    // profiles/round4_experiments.txt, "noclear".)
 #pragma unroll
     for (int lv = 0; lv < kStackLevels; ++lv) stk.pm[lane + 64u * (uint32_t)lv] = make_uint2(0u, 0u);
 #else
@@ -247,15 +238,6 @@ struct DescWalk {
   }
 };
 
-#ifndef SVO_BAND_COLMAJOR
-#define SVO_BAND_COLMAJOR 1
-#endif
-#ifndef SVO_SERPENTINE
-#define SVO_SERPENTINE 1
-#endif
-#ifndef SVO_STEAL_NOW
-#define SVO_STEAL_NOW 0
-#endif
 #ifndef SVO_DRAIN_NUM
 #define SVO_DRAIN_NUM 12
 #endif
@@ -284,7 +266,7 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 // kSpanWords words) in a record of its own in global memory (a.prim: written once per pixel, read once per further frame;
 // registers would cost the kernel its sixth wave per SIMD), and runs frame 0's path, frame 1's, ... from that hit, each with its
 // own random number -- the same operations on the same values in the same order as the (frame, pixel) slots, so the same bytes.
-constexpr uint32_t kSpanWords = 12;   // three uint4 per persistent lane, [wave][3][lane]
+// (kSpanWords, svo_persist_plan.h: three uint4 per persistent lane, [wave][3][lane])
 constexpr uint32_t kSpanSun = 1u << 16;   // in a kSpan lane's `seg`: a miss of the segment under way adds the sun's light
 constexpr uint32_t kKeptMiss = 1u;        // in the last word of a cached record's third plane: the primary ray left the octree
 // kKept (persist_kept_kernel<true>, the fill): the kSpan kernel with a pixel's record in the context's cache (a.kept) instead of
@@ -358,7 +340,7 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
         // left the octree, or the hit of the last segment -- needs no scatter() of its own here: what a miss adds was decided when
         // the ray was set up (kSpanSun, below), and a last hit emits the sums as they stand.  So the lane emits, takes its
         // pixel's next frame (the primary hit from its record, that frame's random number) and shades THAT in the same pass as the
-        // lanes whose primary or inner segment just hit.  (persist_launch: f.bounces >= 2, so a shaded hit always goes on.)
+        // lanes whose primary or inner segment just hit.  (persist_plan: f.bounces >= 2, so a shaded hit always goes on.)
         // (the address is formed here, in the round: hoisted in front of the kernel's loop it is two registers spilled for good)
         uint32_t rl = lane;
         asm volatile("" : "+v"(rl));
@@ -538,8 +520,8 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
     { const unsigned long long now = __builtin_readcyclecounter(); st_shade += now - st_t0; st_part[2] += now - st_r2; st_r2 = now; }
 #endif
     // ---------------- refill idle lanes: ballot + prefix count, one atomic per wave
-    // (a wave whose band is used up tries the next band in its next round; SVO_STEAL_NOW=1 tries it in the same round:
-    // 1-4 % slower -- tools/history/r03_ab_drain.sh)
+    // (a wave whose band is used up tries the next band in its next round; trying it in the same round was a compile-time
+    // experiment: 1-4 % slower -- tools/history/r03_ab_drain.sh, profiles/round3_experiments.txt)
     uint32_t cam_frame = 0u; int cam_sample = 0; bool cam_fresh = false;   // kCams only
     while (bands_left > 0) {
       const unsigned long long idle = __ballot(status == ST_IDLE);
@@ -547,7 +529,6 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
       {
         const uint32_t n = (uint32_t)__builtin_popcountll(idle);
         const int leader = __builtin_ctzll(idle);
-#if SVO_BAND_COLMAJOR
         // a band = a strip of whole tile rows, walked column by column: the pixels in flight on an XCD form a compact
         // block of the screen (strip height x a few dozen tile columns) instead of two or three full-width tile rows
         const int first_row = (int)band * a.rows_per_band;
@@ -556,12 +537,6 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
         const uint32_t band_frame = (uint32_t)(band_rows * f.tiles_x) * 64u;   // pixel slots of the band in one frame
         // ... and over the launch's frames x samples (kSpan: a slot is a pixel, with all its frames)
         const uint32_t band_total = kSpan ? band_frame : band_frame * (uint32_t)(f.batch * a.fold);
-#else
-        const int first_tile = (int)band * a.tiles_per_band;
-        int band_tiles = f.ntiles - first_tile;
-        band_tiles = band_tiles < 0 ? 0 : (band_tiles > a.tiles_per_band ? a.tiles_per_band : band_tiles);
-        const uint32_t band_total = (uint32_t)band_tiles * 64u;
-#endif
         uint32_t base = 0;
         if ((int)lane == leader) base = atomicAdd(a.heads + band * kHeadStride, n);
         base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);   // wave-uniform, and the compiler knows it
@@ -569,7 +544,6 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
             base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
         if (status == ST_IDLE && slot < band_total) {
           const uint32_t l = slot & 63u;
-#if SVO_BAND_COLMAJOR
           // frames of a batch follow one another inside the band: a wave that runs out of frame k goes on with k + 1
           // ; the samples of a pixel (a.fold > 1) follow one another tile by tile: tile 0 sample 0, 1, ..., tile 1 sample 0,
           // ... -- what is in flight at any time are a few tiles' samples, whose primary rays are the same and whose
@@ -594,18 +568,10 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
           int tile_x = (int)udiv_by((uint32_t)j, (uint32_t)band_rows, a.mg_rows[full_band]);
           const int tile_y = first_row + (j - tile_x * band_rows);
           if (a.reverse) tile_x = f.tiles_x - 1 - tile_x;   // serpentine: this frame ends where the next one starts
-#else
-          const int tile = first_tile + (int)(slot >> 6);
-          const int tile_x = tile % f.tiles_x, tile_y = tile / f.tiles_x;
-#endif
           px = tile_x * 8 + (int)(l & 7u);
           py = frame_gy(f, tile_y, (int)(l >> 3));
           if (px < f.width && py < f.y1 && py < f.height) {
-#if SVO_BAND_COLMAJOR
             pix = fi * f.frame_stride + (uint32_t)frame_oy(f, tile_y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px;
-#else
-            pix = (uint32_t)frame_oy(f, tile_y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px;
-#endif
             if (kTab) {
               const float *fr = a.rc + (size_t)fi * a.rc_stride;
               const float2 col = *(const float2 *)(fr + 2 * px);
@@ -614,22 +580,14 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
               d = normalize3(mk(mix_g(ra4.x, rb4.x, col.y), mix_g(ra4.y, rb4.y, col.y), mix_g(ra4.z, rb4.z, col.y)));
               if (kMode == 0) r = rand_of_dot(((float)px + col.x) * 12.9898f + ((float)py + ra4.w) * 78.233f);
             } else if (!kCams) d = primary_direction(f, px, py);
-#if SVO_BAND_COLMAJOR
             seg = a.fold > 1 ? (si << 8) | (fi << 24) : 0u;
-#else
-            seg = 0u;
-#endif
             mask = mk(1.f, 1.f, 1.f);
             accum = mk(0.f, 0.f, 0.f);
             normal = mk(0.f, 0.f, 0.f);
             value = 0u;
             depth = 0.0f;
-#if SVO_BAND_COLMAJOR
             if (kMode == 0 && !kCams && !kTab) r = pixel_rand((float)px, (float)py, (float)(f.frame_number + (int)fi + a.sample + (int)si));
             if (kCams) { cam_frame = fi; cam_sample = a.sample + (int)si; cam_fresh = true; }
-#else
-            if (kMode == 0) r = pixel_rand((float)px, (float)py, (float)(f.frame_number + a.sample));
-#endif
             ninit = true; icone = false; io = cam_o; its = beam_start(f, px, py);
             status = ST_ACTIVE;   // taken (the set-up below gives the real status)
           }
@@ -662,12 +620,8 @@ __device__ __forceinline__ void persist_body(const PersistArgs &a, typename Walk
 #ifdef SVO_STAMPS
           if (bands_left == 0) st_dry = __builtin_amdgcn_s_memrealtime();
 #endif
-#if !SVO_STEAL_NOW
-          break;
-#endif
-        } else {
-          break;
         }
+        break;
       }
     }
 #ifdef SVO_STAMPS
@@ -749,7 +703,6 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_span_k
   persist_body<0, DescWalk, false, kTab, true>(a, stk);
 }
 
-#if SVO_BAND_COLMAJOR
 // The reuse of the context's primary-hit cache (persist_kept_kernel<false>): the kSpan kernel of a launch whose primary hits an
 // earlier launch of the same camera, pool and frame left in a.kept (the fill).  A refilled lane casts nothing: it loads its
 // pixel's record and shades frame 0 from it exactly as the kSpan kernel shades frames 1.. from its lane's own -- the same
@@ -875,7 +828,7 @@ __device__ __forceinline__ void persist_reuse_body(const PersistArgs &a, DescWal
       if (!again || __ballot(status == ST_IDLE) == 0ull) break;
     }
 
-    // ---------------- one shading pass: a hit the path goes on from (persist_launch: f.bounces >= 2), persist_body's kSpan shading
+    // ---------------- one shading pass: a hit the path goes on from (persist_plan: f.bounces >= 2), persist_body's kSpan shading
     bool ninit = false;
     if (shade) {
       const bool mirror = ((f.mirror_mask >> (hvalue & 31u)) & 1u) != 0u;
@@ -908,7 +861,7 @@ __device__ __forceinline__ void persist_reuse_body(const PersistArgs &a, DescWal
   }
 }
 
-// a static-camera batch of mode 0 whose primary hits stay in the context's cache from launch to launch (persist_launch chooses):
+// a static-camera batch of mode 0 whose primary hits stay in the context's cache from launch to launch (persist_kept_choose):
 // kFill = the kSpan kernel writing the cache, !kFill = the kernel that reads it and casts no primary ray
 template <bool kFill>
 __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_kept_kernel(const PersistArgs a) {
@@ -916,23 +869,16 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_kept_k
   if constexpr (kFill) persist_body<0, DescWalk, false, true, true, true>(a, stk);
   else persist_reuse_body(a, stk);
 }
-#endif
 
 // a.fold > 1: tiles per group of a band's walk.  1 / 8 / 64 / 512 / all: 4.47 / 4.49 / 4.47 / 4.41 / 4.20 Grays/s at 64
 // samples per pixel (tools/history/r03_fold2.sh): a group's samples should be in flight together, not a whole band's
 constexpr int kFoldGroup = 8;
-// Persistent waves per CU and launch when several launches share the GPU (a ring of more than one slot): the next launch's
-// waves take the CUs the previous launch's tail frees.  Swept in rounds 2-4 (profiles/round4_experiments.txt: 10 waves with
-// a round once at most 9/16 of the lanes are still traversing is the shape every headline number was measured on; 16 waves: -6 %).
-constexpr int kRingWavesPerCu = 10;
-// ... and when svo_dispatch_async takes turns on n {stream, image} sets (the reference's loop: one frame per launch, up to n
-// launches in flight): waves per CU and launch by n -- about 32 / n, the best of tools/loop_shape.py's sweeps
-// (profiles/round6_experiments.txt: 2 sets 12, 3 sets 10, 4 sets 8, 5 and more 6)
-inline int overlap_waves_per_cu(int sets) { return sets <= 2 ? 12 : sets == 3 ? 10 : sets == 4 ? 8 : 6; }
 constexpr int kHeadSets = 8;   // counter sets: one per frame in flight (its sample launches follow one another on one
                                // stream and share it), reused round-robin
 constexpr int kFaccSets = 4;   // colour-sum buffers (spp > 1): one per frame, reused round-robin
 
+// The device buffers of the context's launches, their events and flags: made at the first launch, gone with every svo_resize
+// (persist_free).  What must outlive a resize is in PersistSettings / PersistLimits (svo_persist_plan.h).
 struct PersistBuffers {
   uint32_t *heads = nullptr;
   // a counter set / colour-sum buffer may still be in use by a frame in flight on another stream when the ring
@@ -944,22 +890,12 @@ struct PersistBuffers {
   hipEvent_t facc_done[kFaccSets] = {};
   bool facc_used[kFaccSets] = {};
   size_t facc_floats = 0;   // floats in each colour-sum buffer
-  int blocks = 0;
-  int thresh_num = 0;   // sixteenths; 0 = the running kernel's default: 9 for persist_kernel (8 / 9 / 10 / 11: 4.28 / 4.38 / 4.33 /
-                        // 4.14 Grays/s, tools/history/sweep8.sh), SVO_SPARE_THRESH for the spare-ray kernel
-  int spare_mode = 0;   // 1 = the spare-ray kernel (variants/svo_persist2.hip.h) on walkable pools (environment SVO_SPARE=1: round 5's
-                        // experiment, measured slower than persist_kernel with launches in flight); 0 = persist_kernel everywhere
-  const float4 *ntab = nullptr;   // the context's normal table (made with the context; survives persist_free)
-  int ntab_mode = 1;              // environment SVO_NORMAL_TABLE=0: decode in place
-  int table_mode = 1;   // 1 = row / column tables + the kTab kernels where they apply (environment SVO_RC_TABLE=0: all in the rounds)
-  float *rc[8] = {};           // row / column tables, one buffer per counter set (a set's launches are ordered by its event)
-  size_t rc_floats[8] = {};
-  uint32_t *prec[8] = {};      // path records of the spare-ray kernel, one buffer per counter set
+  float *rc[kHeadSets] = {};   // row / column tables, one buffer per counter set (a set's launches are ordered by its event)
+  size_t rc_floats = 0;        // floats in each
+  uint32_t *prec[kHeadSets] = {};   // path records of the spare-ray kernel, one buffer per counter set
   size_t prec_words = 0;
-  int span_mode = 1;   // 1 = a static-camera batch of mode 0 casts its primary rays once (persist_span_kernel); environment
-                       // SVO_BATCH_PRIMARY=0: every frame of the batch casts its own
-  uint4 *prim[8] = {};         // primary-hit records of persist_span_kernel's lanes, one buffer per counter set
-  size_t prim_waves = 0;       // persistent waves each of them has room for
+  uint4 *prim[kHeadSets] = {};      // primary-hit records of persist_span_kernel's lanes, one buffer per counter set
+  size_t prim_waves = 0;            // persistent waves each of them has room for
   // The primary-hit cache (persist_kept_kernel): ONE buffer for the context, whatever counter set a launch runs on.  What a
   // primary hit depends on is its key; a launch whose key equals the cache's reads it once the fill has been SEEN complete
   // (hipEventQuery; nothing here ever waits), a launch with another key fills it once the buffer is idle -- the last fill and
@@ -970,7 +906,6 @@ struct PersistBuffers {
     uint32_t pool_len, cam[15];
     int32_t width, height, y0, y1, row_step, out_y0, tiles_y;
   };
-  int kept_mode = 1;           // svo_set_primary_cache
   uint4 *kept = nullptr;
   size_t kept_cap = 0;         // records per plane the buffer has room for
   size_t kept_failed = 0;      // ... and the size hipMalloc last refused: launches of that size and larger stay on persist_span_kernel
@@ -979,19 +914,15 @@ struct PersistBuffers {
   bool kept_fill_inflight = false;   // a fill was launched and kept_filled not yet seen complete
   hipEvent_t kept_filled = nullptr;
   bool kept_reader[kHeadSets] = {};  // the set's head_done is behind a launch that read the cache (or behind one that waited for it)
-  uint64_t pool_epoch = 0;     // bumped by everything that changes the pool (svo_hip.hip::pool_changed)
-  uint64_t kept_fills = 0, kept_reuses = 0;
-  int last_thresh = 9;
-  int waves_per_cu = 0;     // 0 = automatic: as many as fit (occupancy query) for one launch at a time, kRingWavesPerCu for
-                             // the submissions of a ring with more than one slot (in_ring, set around the launch by ring_submit)
-  bool in_ring = false;
-  bool in_overlap = false;   // set around the launch by svo_dispatch_async while it takes turns on several image sets ...
-  int overlap_sets = 4;      // ... and on how many
-  int last_blocks = 0, last_per_cu = 0;   // shape of the last launch (svo_launch_info)
-  int max_per_cu = 16, max_per_cu_desc = 16, cus = 256;   // resident waves per CU: byte walk / descriptor walk
-  int max_per_cu_spare = 0;                               // ... / the spare-ray kernel (0 = not asked yet)
-  int cus_reserved = 0;   // CUs the launching stream may not use (svo_set_reserved_cus): fewer persistent waves
+  int last_thresh = 9, last_blocks = 0, last_per_cu = 0;   // shape of the last launch (svo_launch_info)
   unsigned launches = 0, frames = 0;
+};
+
+// everything the persistent pipeline keeps for a context
+struct PersistState {
+  PersistSettings set;
+  PersistLimits lim;
+  PersistBuffers buf;
 };
 
 inline void persist_free(PersistBuffers &b) {
@@ -1004,13 +935,26 @@ inline void persist_free(PersistBuffers &b) {
   for (auto &e : b.facc_done) if (e) (void)hipEventDestroy(e);
   if (b.kept) (void)hipFree(b.kept);
   if (b.kept_filled) (void)hipEventDestroy(b.kept_filled);
-  const int wpc = b.waves_per_cu, th = b.thresh_num, sm = b.spare_mode, tm = b.table_mode;   // tuning survives a resize
-  const float4 *nt = b.ntab;
-  const int nm = b.ntab_mode, sp = b.span_mode, km = b.kept_mode;
-  const uint64_t ep = b.pool_epoch, kf = b.kept_fills, kr = b.kept_reuses;   // (so do the counts svo_primary_cache_info reports)
   b = PersistBuffers();
-  b.waves_per_cu = wpc; b.thresh_num = th; b.spare_mode = sm; b.table_mode = tm; b.ntab = nt; b.ntab_mode = nm; b.span_mode = sp;
-  b.kept_mode = km; b.pool_epoch = ep; b.kept_fills = kf; b.kept_reuses = kr;
+}
+
+// Grows a family of equally sized device buffers to `bytes` each: nothing in flight may still use the old ones, so the device is
+// waited for; then all are freed, `have` (and their in-use flags, if they have any) cleared, and all allocated anew.  `have`
+// becomes `want` only behind the last allocation: a failed grow leaves nothing half-sized, and the next launch grows again.
+template <class T, size_t N>
+inline hipError_t grow_device_buffers(T *(&bufs)[N], bool *used, size_t &have, size_t want, size_t bytes) {
+  hipError_t e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+  for (size_t i = 0; i < N; i++) {
+    if (bufs[i]) (void)hipFree(bufs[i]);
+    bufs[i] = nullptr;
+    if (used) used[i] = false;
+  }
+  have = 0;
+  for (size_t i = 0; i < N; i++)
+    if ((e = hipMalloc((void **)&bufs[i], bytes)) != hipSuccess) return e;
+  have = want;
+  return hipSuccess;
 }
 
 // the cache describes nothing any more (the pool changed, the host opted out).  The buffer and what is known about the launches
@@ -1100,9 +1044,6 @@ template <int kMode>
 inline void persist2_launch_mode(const PersistArgs &a, int blocks, hipStream_t stream);
 inline hipError_t persist2_occupancy(int *per_cu);
 #endif
-#ifndef SVO_SPARE_THRESH
-#define SVO_SPARE_THRESH 13
-#endif
 // SVO_SPARE_RECORDS: 0 = the two path records of a lane live in registers (18 each; the kernel then runs 4 waves per SIMD),
 // 1 = in global memory (6 waves per SIMD; measured: the records' traffic -- 144 bytes per ray written and read back, more
 // than the caches hold with six launches in flight -- costs more than the lanes gained: profiles/round5_experiments.txt)
@@ -1115,14 +1056,12 @@ inline void persist_launch_mode(const PersistArgs &a, int blocks, hipStream_t st
 #if SVO_HAVE_SPARE
   if (a.spare) { persist2_launch_mode<kMode>(a, blocks, stream); return; }
 #endif
-  if (kMode == 0 && a.span) {   // (persist_launch: mode 0, one camera, the descriptor walk; any other mode runs its own kernel)
-#if SVO_BAND_COLMAJOR
-    if (a.kept) {   // (persist_launch: only with the tables)
+  if (kMode == 0 && a.span) {   // (persist_plan: mode 0, one camera, the descriptor walk; any other mode runs its own kernel)
+    if (a.kept) {   // (persist_plan: only with the tables)
       if (a.kept_fill) hipLaunchKernelGGL((persist_kept_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
       else hipLaunchKernelGGL((persist_kept_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
       return;
     }
-#endif
     if (a.rc) hipLaunchKernelGGL((persist_span_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((persist_span_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, a);
     return;
@@ -1180,262 +1119,247 @@ __global__ __launch_bounds__(64) void persist_resolve_sequence_kernel(const Fram
   color[pix] = last;
 }
 
-// can `n` samples (or frames of a progressive sequence) per pixel be carried by one launch of `f`?
-inline bool persist_can_fold(const Frame &f, int n) {
-  const unsigned long long nb = (unsigned long long)(f.batch > 1 ? f.batch : 1);
-  const unsigned long long bytes = 192ull * (unsigned long long)n * (unsigned long long)f.ntiles * nb * sizeof(float);
+// the most bytes of sample slots one launch may ask for (persist_can_fold); a variants build reads the environment's, once
+inline unsigned long long persist_fold_budget() {
 #if SVO_VARIANTS
-  static const unsigned long long budget = getenv("SVO_FOLD_BYTES") ? strtoull(getenv("SVO_FOLD_BYTES"), nullptr, 10) : (4ull << 30);
+  static const unsigned long long budget = getenv("SVO_FOLD_BYTES") ? strtoull(getenv("SVO_FOLD_BYTES"), nullptr, 10) : kFoldBytes;
+  return budget;
 #else
-  const unsigned long long budget = 4ull << 30;
+  return kFoldBytes;
 #endif
-  return SVO_BAND_COLMAJOR && n > 1 && f.bounces <= 255 && bytes <= budget && f.batch <= 255 && n < 65536 &&
-         (long long)f.ntiles * (long long)nb * n < (1ll << 25);
 }
 
-// `out_npix` = elements of the output images: W*H, or more when packed stripes overhang the frame (caller-owned
-// gather buffers); the colour-sum planes are indexed like the outputs.
-// `desc` / `aux` / `desc_count`: the interior-descriptor table of the pool (svo_derive.hip.h), or null = walk the records
-inline int persist_launch(PersistBuffers &b, const uint8_t *pool, const Frame &f, uint32_t *color, float *depth,
-                          uint4 *hits, size_t out_npix, hipStream_t stream, const uint2 *desc = nullptr,
-                          const uint2 *aux = nullptr, uint32_t desc_count = 0, FrameVar *fvar = nullptr,
-                          const FrameVar *fvar_host = nullptr, int (*copy_cams)(void *) = nullptr, void *copy_arg = nullptr) {
+// What one launch is given besides its Frame.
+struct PersistLaunch {
+  const uint8_t *pool = nullptr;
+  uint32_t *color = nullptr;
+  float *depth = nullptr;
+  uint4 *hits = nullptr;
+  size_t out_npix = 0;   // elements of the output images: W*H, or more when packed stripes overhang the frame (caller-owned
+                         // gather buffers); the colour-sum planes are indexed like the outputs
+  hipStream_t stream = nullptr;
+  LaunchShape shape = kPlain;   // who shares the GPU with the launch (svo_persist_plan.h) ...
+  int overlap_sets = 0;         // ... kOverlap: the number of image sets taking turns
+  // the interior-descriptor table of the pool (svo_derive.hip.h), or null = walk the records
+  const uint2 *desc = nullptr, *aux = nullptr;
+  uint32_t desc_count = 0;
+  const float4 *ntab = nullptr;   // the context's normal table, or null = the kernels decode in place
   // fvar: where the launch's per-frame cameras live on the device (null: one camera, f.cam); fvar_host: the same on the host.  They
   // reach the device inside the table kernel's arguments when the launch has one and they fit (kCamPack), else through copy_cams
-  // (the caller's staged copy on `stream`), called here in front of the first kernel that reads them.
-  // the colour-sum planes are indexed like the outputs: a batch needs room for all its frames
-  const size_t npix = f.batch > 1 ? std::max(out_npix, (size_t)f.batch * (size_t)f.frame_stride) : out_npix;
+  // (the caller's staged copy on `stream`), called in front of the first kernel that reads them.
+  FrameVar *fvar = nullptr;
+  const FrameVar *fvar_host = nullptr;
+  int (*copy_cams)(void *) = nullptr;
+  void *copy_arg = nullptr;
+};
+
+// The buffers' first use: the counter sets and the events.  The context's first use: what the device offers, and in a
+// variants build the experiment knobs of the environment (they override svo_set_tuning: libsvohip_variants.so only).
+inline hipError_t persist_prepare(PersistState &p) {
+  PersistBuffers &b = p.buf;
   hipError_t e;
   if (!b.heads) {
-    if ((e = hipMalloc((void **)&b.heads, kHeadSets * kHeadWords * sizeof(uint32_t))) != hipSuccess) return (int)e;
+    if ((e = hipMalloc((void **)&b.heads, kHeadSets * kHeadWords * sizeof(uint32_t))) != hipSuccess) return e;
     for (auto &ev : b.head_done)
-      if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return (int)e;
+      if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
     for (auto &ev : b.facc_done)
-      if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return (int)e;
+      if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+  }
+  if (!p.lim.known) {
     int dev = 0, cus = 256, per_cu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persist_kernel<0, ByteWalk>, 64, 0) != hipSuccess || per_cu < 1)
       per_cu = 16;
-    b.max_per_cu = per_cu;
+    p.lim.max_per_cu = per_cu;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, persist_kernel<0, DescWalk>, 64, 0) != hipSuccess || per_cu < 1)
       per_cu = 16;
-    b.max_per_cu_desc = per_cu;
-    b.cus = cus;
+    p.lim.max_per_cu_desc = per_cu;
+    p.lim.cus = cus;
+    p.lim.known = true;
 #if SVO_VARIANTS
-    // experiment knobs (override svo_set_tuning): libsvohip_variants.so only
-    if (const char *e1 = getenv("SVO_PERSIST_WAVES_PER_CU")) b.waves_per_cu = atoi(e1);
-    if (const char *e2 = getenv("SVO_PERSIST_THRESH")) b.thresh_num = atoi(e2);
-    if (const char *e3 = getenv("SVO_SPARE")) b.spare_mode = atoi(e3) != 0 ? 1 : 0;
-    if (const char *e4 = getenv("SVO_RC_TABLE")) b.table_mode = atoi(e4) != 0 ? 1 : 0;
-    if (const char *e5 = getenv("SVO_NORMAL_TABLE")) b.ntab_mode = atoi(e5) != 0 ? 1 : 0;
-    if (const char *e6 = getenv("SVO_BATCH_PRIMARY")) b.span_mode = atoi(e6) != 0 ? 1 : 0;
+    PersistSettings &s = p.set;
+    if (const char *e1 = getenv("SVO_PERSIST_WAVES_PER_CU")) s.waves_per_cu = atoi(e1);
+    if (const char *e2 = getenv("SVO_PERSIST_THRESH")) s.thresh_num = atoi(e2);
+    if (const char *e3 = getenv("SVO_SPARE")) s.spare_mode = atoi(e3) != 0 ? 1 : 0;
+    if (const char *e4 = getenv("SVO_RC_TABLE")) s.table_mode = atoi(e4) != 0 ? 1 : 0;
+    if (const char *e5 = getenv("SVO_NORMAL_TABLE")) s.ntab_mode = atoi(e5) != 0 ? 1 : 0;
+    if (const char *e6 = getenv("SVO_BATCH_PRIMARY")) s.span_mode = atoi(e6) != 0 ? 1 : 0;
 #endif
   }
-  // the spare-ray kernel walks the descriptor table in assembly: pools the table cannot state, and builds with hipcc's
-  // translation of the loop (SVO_ASM_LOOP=0), run persist_kernel
-  const bool spare_kernel = SVO_HAVE_SPARE && b.spare_mode != 0 && desc != nullptr;
+  return hipSuccess;
+}
+
+// The primary-hit cache's say in a launch the plan names a candidate (`need` = plan.kept_records): a.kept and a.kept_fill when
+// the launch reads or fills the cache, a.kept = null when it runs persist_span_kernel as before.  An allocation that fails is no
+// error: launches of that size stay on today's kernel.
+inline hipError_t persist_kept_choose(PersistState &p, const PersistLaunch &in, const Frame &f, size_t need, PersistArgs &a) {
+  PersistBuffers &b = p.buf;
+  PersistBuffers::KeptKey key;
+  memset(&key, 0, sizeof key);
+  key.pool = in.pool; key.desc = in.desc; key.pool_epoch = p.set.pool_epoch; key.pool_len = f.pool_len;
+  memcpy(key.cam, f.cam, sizeof key.cam);
+  key.width = f.width; key.height = f.height; key.y0 = f.y0; key.y1 = f.y1; key.row_step = f.row_step; key.out_y0 = f.out_y0;
+  key.tiles_y = f.tiles_y;
+  if (b.kept_valid && memcmp(&key, &b.kept_key, sizeof key) == 0) {
+    if (persist_kept_filled(b)) a.kept = b.kept;
+  } else if ((b.kept_failed == 0 || need < b.kept_failed) && need < (1ull << 30) && persist_kept_idle(b)) {
+    b.kept_valid = false;
+    if (!b.kept_filled && hipEventCreateWithFlags(&b.kept_filled, hipEventDisableTiming) != hipSuccess) {
+      b.kept_filled = nullptr;
+      (void)hipGetLastError();
+    } else if (b.kept_cap < need) {   // (idle, so nothing reads the old buffer; the wait is the one `prim` grows behind)
+      hipError_t e;
+      if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+      if (b.kept) (void)hipFree(b.kept);
+      b.kept = nullptr; b.kept_cap = 0;
+      if (hipMalloc((void **)&b.kept, 3 * need * sizeof(uint4)) == hipSuccess) b.kept_cap = need;
+      else { b.kept = nullptr; b.kept_failed = need; (void)hipGetLastError(); }
+    }
+    if (b.kept_filled && b.kept_cap >= need) { a.kept = b.kept; a.kept_fill = 1; b.kept_key = key; }
+  }
+  a.kept_n = (uint32_t)b.kept_cap; a.kept_origin = (uint32_t)f.out_y0 * (uint32_t)f.width;
+  return hipSuccess;
+}
+// ... and behind the launch on counter set `hset`: a fill's event and key, a reader's mark on its set
+inline hipError_t persist_kept_launched(PersistState &p, const PersistArgs &a, int hset, hipStream_t stream) {
+  PersistBuffers &b = p.buf;
+  if (a.kept && a.kept_fill) {
+    const hipError_t e = hipEventRecord(b.kept_filled, stream);
+    if (e != hipSuccess) return e;
+    b.kept_valid = true; b.kept_fill_inflight = true; p.set.kept_fills++;
+  } else if (a.kept) {
+    b.kept_reader[hset] = true; p.set.kept_reuses++;
+  }
+  return hipSuccess;
+}
+
+// the kernels' arguments, for a launch on counter set `hset` (a.reverse and a.sample: per kernel launch; the cache: persist_kept_choose)
+inline PersistArgs persist_args(const PersistPlan &plan, const Frame &f, const PersistLaunch &in, const PersistBuffers &b, int hset, float *facc) {
+  PersistArgs a;
+  a.pool = in.pool; a.f = f; a.color = in.color; a.depth = in.depth; a.hits = in.hits; a.facc = facc; a.npix = plan.npix;
+  a.heads = b.heads + (size_t)hset * kHeadWords;
+  a.tiles_per_band = (f.ntiles + 7) / 8;
+  a.rows_per_band = plan.rows_per_band;
+  a.reverse = 0; a.sample = 0;
+  a.thresh_num = plan.thresh_num;
+  a.fold = plan.fold;
+  a.group = kFoldGroup;
+  memcpy(a.mg_rows, plan.mg_rows, sizeof a.mg_rows);
+  memcpy(a.mg_tpf, plan.mg_tpf, sizeof a.mg_tpf);
+  a.desc = in.desc; a.aux = in.aux; a.desc_count = in.desc_count;
+  a.fvar = in.fvar;
+  // (a counter set's launches are ordered by the set's event: so are its path records, primary-hit records and tables)
+  a.prec = (plan.spare && SVO_SPARE_RECORDS) ? b.prec[hset] : nullptr;
+  a.spare = plan.spare ? 1 : 0;
+  a.span = plan.span ? 1 : 0;
+  a.prim = plan.span ? b.prim[hset] : nullptr;
+  a.rc = plan.tables ? b.rc[hset] : nullptr;
+  a.rc_stride = (uint32_t)plan.rc_stride;
+  a.ntab = in.ntab;
+  a.kept = nullptr; a.kept_n = 0; a.kept_origin = 0; a.kept_fill = 0;
+  return a;
+}
+
+// the colour sums of a launch become rgba8: by plane, by tile (folded samples) or frame after frame (a folded sequence)
+inline void persist_resolve(const PersistPlan &plan, const Frame &f, const PersistLaunch &in, const float *facc) {
+  const unsigned nb = (unsigned)(f.batch > 1 ? f.batch : 1);
+  if (plan.resolve == PersistPlan::kSequence) {
+    hipLaunchKernelGGL(persist_resolve_sequence_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y), dim3(64), 0, in.stream, f, facc, plan.fold, in.color);
+  } else if (plan.resolve == PersistPlan::kTiles) {
+    hipLaunchKernelGGL(persist_resolve_tiles_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y, nb), dim3(64), 0, in.stream, f, facc, plan.fold, in.color);
+  } else {
+    dim3 grid((unsigned)((f.width + 255) / 256), (unsigned)(f.tiles_y * 8), nb);
+    hipLaunchKernelGGL(persist_resolve_kernel, grid, dim3(256), 0, in.stream, f, facc, plan.npix, in.color);
+  }
+}
+
+// One frame (or batch, or folded sequence) of `f` as `in` says: what is launched is persist_plan's decision, made here once.
+inline int persist_launch(PersistState &p, const Frame &f, const PersistLaunch &in) {
+  PersistBuffers &b = p.buf;
+  hipError_t e;
+  if ((e = persist_prepare(p)) != hipSuccess) return (int)e;
+  const bool has_table = in.desc != nullptr;
 #if SVO_HAVE_SPARE
-  if (spare_kernel && b.max_per_cu_spare == 0) {
+  if (persist_uses_spare(p.set, has_table, true) && p.lim.max_per_cu_spare == 0) {
     int per_cu = 0;
     if (persist2_occupancy(&per_cu) != hipSuccess || per_cu < 1) per_cu = 16;
-    b.max_per_cu_spare = per_cu;
+    p.lim.max_per_cu_spare = per_cu;
   }
 #endif
-  if (spare_kernel && SVO_SPARE_RECORDS) {
-    const size_t need = (size_t)b.cus * (size_t)b.max_per_cu_desc * (size_t)(2 * 18 * 64);   // = kRecWaveWords per wave that fits
-    if (b.prec_words < need) {
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;
-      for (auto &p : b.prec) { if (p) (void)hipFree(p); p = nullptr; }
-      b.prec_words = 0;
-      for (auto &p : b.prec)
-        if ((e = hipMalloc((void **)&p, need * sizeof(uint32_t))) != hipSuccess) return (int)e;
-      b.prec_words = need;
-    }
+  const PersistPlan plan = persist_plan(p.set, p.lim, f, in.shape, in.overlap_sets, has_table, in.fvar != nullptr, SVO_HAVE_SPARE != 0,
+                                        in.out_npix, persist_fold_budget());
+  if (plan.spare && SVO_SPARE_RECORDS) {
+    const size_t need = (size_t)p.lim.cus * (size_t)p.lim.max_per_cu_desc * (size_t)(2 * 18 * 64);   // = kRecWaveWords per wave that fits
+    if (b.prec_words < need && (e = grow_device_buffers(b.prec, nullptr, b.prec_words, need, need * sizeof(uint32_t))) != hipSuccess)
+      return (int)e;
   }
-  {
-    const int fill = spare_kernel ? b.max_per_cu_spare : (desc ? b.max_per_cu_desc : b.max_per_cu);
-    int per_cu = b.waves_per_cu > 0 ? b.waves_per_cu : (b.in_ring ? std::min(kRingWavesPerCu, fill) : (b.in_overlap ? std::min(overlap_waves_per_cu(b.overlap_sets), fill) : fill));
-    b.blocks = (b.cus - b.cus_reserved) * per_cu;
-    b.last_per_cu = per_cu;
-  }
-  const int spp = f.spp < 1 ? 1 : f.spp;
-  const bool resolve = spp > 1 || f.progressive;   // colours go through the float planes and the resolve kernel
-  float *facc = nullptr;
+  b.last_per_cu = plan.per_cu;
   const unsigned frame_no = b.frames++;
+  if (plan.invalid) return (int)hipErrorInvalidValue;
+  const bool resolve = plan.resolve != PersistPlan::kNone;
+  float *facc = nullptr;
   int fset = 0;
-  // All samples of a frame in ONE launch when their slots fit (3 floats per pixel and sample, kFaccSets times): the
-  // launch's bands hold the frame's samples one after the other like the frames of a batch, a wave goes from sample to
-  // sample without a tail, and the sums cost one store per sample instead of a read-modify-write.  Otherwise one launch
-  // per sample.  Same bytes either way (tests/test_gpu_inflight.py).
-  int fold = 1;
-  unsigned long long slots = 0;
-  const bool sequence = f.progressive && f.seq > 1;   // the caller has checked persist_can_fold(f, f.seq) and spp == 1
-  const int per_pixel = sequence ? f.seq : spp;
-  if (persist_can_fold(f, per_pixel)) {
-    fold = per_pixel;
-    slots = 192ull * (unsigned long long)fold * (unsigned long long)f.ntiles * (f.batch > 1 ? f.batch : 1);
-  }
-  if (sequence && (fold != f.seq || spp != 1)) return (int)hipErrorInvalidValue;
-  if (resolve) {
-    const size_t need = fold > 1 ? (size_t)slots : 3 * npix;   // floats per buffer
-    if (b.facc_floats < need) {   // grow: nothing may still be summing into the old buffers
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;
-      for (int i = 0; i < kFaccSets; i++) {
-        if (b.facc[i]) (void)hipFree(b.facc[i]);
-        b.facc[i] = nullptr;
-        b.facc_used[i] = false;
-      }
-      b.facc_floats = 0;
-      for (int i = 0; i < kFaccSets; i++)
-        if ((e = hipMalloc((void **)&b.facc[i], need * sizeof(float))) != hipSuccess) return (int)e;
-      b.facc_floats = need;
-    }
+  if (resolve) {   // grow: nothing may still be summing into the old buffers
+    if (b.facc_floats < plan.facc_floats &&
+        (e = grow_device_buffers(b.facc, b.facc_used, b.facc_floats, plan.facc_floats, plan.facc_floats * sizeof(float))) != hipSuccess)
+      return (int)e;
     fset = (int)(frame_no % kFaccSets);
     facc = b.facc[fset];
-    if (b.facc_used[fset] && (e = hipStreamWaitEvent(stream, b.facc_done[fset], 0)) != hipSuccess) return (int)e;
+    if (b.facc_used[fset] && (e = hipStreamWaitEvent(in.stream, b.facc_done[fset], 0)) != hipSuccess) return (int)e;
   }
-  PersistArgs a;
-  a.pool = pool; a.f = f; a.color = color; a.depth = depth; a.hits = hits; a.facc = facc; a.npix = npix;
-  a.tiles_per_band = (f.ntiles + 7) / 8;
-  a.rows_per_band = (f.tiles_y + 7) / 8;
-  a.thresh_num = b.thresh_num > 0 ? b.thresh_num : (spare_kernel ? SVO_SPARE_THRESH : 9);
-  b.last_thresh = a.thresh_num;
-  a.fold = fold;
-  a.group = kFoldGroup;
-  a.desc = desc; a.aux = aux; a.desc_count = desc_count;
-  a.fvar = fvar;
-  // Consecutive frame numbers under one camera (the reference's still camera: frameNumber advances only while the camera stands,
-  // Main.java:225-233) share their primary rays in mode 0: one slot per pixel, the primary cast once for the whole batch.  Frames
-  // with their own cameras, several samples per pixel (folded or a launch each) / sequences, beam launches, paths of the primary
-  // ray alone (every frame of those is the same image), the record walk and the spare-ray kernel keep a slot per (frame, pixel).
-  const bool span = SVO_BAND_COLMAJOR && b.span_mode != 0 && f.render_mode == 0 && fvar == nullptr && fold == 1 && !resolve &&
-                    f.batch > 1 && f.bounces >= 2 && f.use_beam == 0 && desc != nullptr && !spare_kernel;
-  a.span = span ? 1 : 0;
-  const int slot_frames = span ? 1 : (f.batch > 1 ? f.batch : 1);   // frames a band's slots are counted over
-  {
-    const int last_rows = a.rows_per_band > 0 ? f.tiles_y % a.rows_per_band : 0;   // the one band that is not full (if any)
-    const uint32_t tpf[2] = {(uint32_t)(a.rows_per_band * f.tiles_x * fold), (uint32_t)(last_rows * f.tiles_x * fold)};
-    const uint64_t nb = (uint64_t)slot_frames;
-    a.mg_rows[0] = udiv_magic((uint32_t)a.rows_per_band, (uint64_t)a.rows_per_band * (uint64_t)f.tiles_x);
-    a.mg_rows[1] = udiv_magic((uint32_t)last_rows, (uint64_t)last_rows * (uint64_t)f.tiles_x);
-    a.mg_tpf[0] = udiv_magic(tpf[0], nb * tpf[0]);   // n = slot >> 6 < frames x tile slots per frame
-    a.mg_tpf[1] = udiv_magic(tpf[1], nb * tpf[1]);
-  }
-  const long long work = (long long)f.ntiles * slot_frames * fold;
-  const int blocks = work < (long long)b.blocks ? (int)work : b.blocks;
-  b.last_blocks = blocks;
-  if (span && b.prim_waves < (size_t)blocks) {   // grow all sets at once, for as many waves as a launch of this shape can have
-    const size_t waves = (size_t)std::max(b.blocks, blocks);
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;   // (launches in flight may still use the old records)
-    for (auto &p : b.prim) { if (p) (void)hipFree(p); p = nullptr; }
-    b.prim_waves = 0;
-    for (auto &p : b.prim)
-      if ((e = hipMalloc((void **)&p, waves * 64 * kSpanWords * sizeof(uint32_t))) != hipSuccess) return (int)e;
-    b.prim_waves = waves;
-  }
+  b.last_thresh = plan.thresh_num;
+  b.last_blocks = plan.blocks;
+  // (launches in flight may still use the old records)
+  if (plan.span && b.prim_waves < (size_t)plan.blocks &&
+      (e = grow_device_buffers(b.prim, nullptr, b.prim_waves, plan.prim_waves, plan.prim_waves * 64 * kSpanWords * sizeof(uint32_t))) != hipSuccess)
+    return (int)e;
   // a ring of counter sets: frames may be in flight on different streams at the same time.  A frame's sample launches
   // are ordered by its stream, so they share the frame's set; only another frame's re-use waits (for the event)
   const int hset = (int)(frame_no % kHeadSets);
-  a.heads = b.heads + (size_t)hset * kHeadWords;
-  a.prec = (spare_kernel && SVO_SPARE_RECORDS) ? b.prec[hset] : nullptr;   // (a counter set's launches are ordered by the set's event: so are its records)
-  a.spare = spare_kernel ? 1 : 0;
-  a.prim = span ? b.prim[hset] : nullptr;   // (likewise)
-  // the row / column tables: launches that carry one sample per pixel (samples / sequences folded into a launch seed every
-  // sample of a pixel differently and keep computing in the round), on the descriptor walk, not the spare-ray kernel
-  a.rc = nullptr; a.rc_stride = 0;
-  a.ntab = b.ntab_mode != 0 ? b.ntab : nullptr;
-  if (b.table_mode != 0 && desc != nullptr && !spare_kernel && fold == 1) {
-    const size_t stride = (size_t)((2 * f.width + 3) & ~3) + 8 * (size_t)f.height, need = stride * (size_t)(f.batch > 1 ? f.batch : 1);
-    if (b.rc_floats[hset] < need) {   // grow all sets at once (one wait for the device, not one per set inside a run)
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;   // (launches in flight may still read the old tables)
-      for (int i = 0; i < kHeadSets; i++) {
-        if (b.rc[i]) (void)hipFree(b.rc[i]);
-        b.rc[i] = nullptr; b.rc_floats[i] = 0;
-      }
-      for (int i = 0; i < kHeadSets; i++) {
-        if ((e = hipMalloc((void **)&b.rc[i], need * sizeof(float))) != hipSuccess) return (int)e;
-        b.rc_floats[i] = need;
-      }
-    }
-    a.rc = b.rc[hset]; a.rc_stride = (uint32_t)stride;
-  }
-  // the primary-hit cache: static-camera batches without hit records (those would need a fourth plane), on the tables' kernels
-  a.kept = nullptr; a.kept_n = 0; a.kept_origin = 0; a.kept_fill = 0;
-  if (SVO_BAND_COLMAJOR && span && b.kept_mode != 0 && f.write_hits == 0 && a.rc != nullptr) {
-    PersistBuffers::KeptKey key;
-    memset(&key, 0, sizeof key);
-    key.pool = pool; key.desc = desc; key.pool_epoch = b.pool_epoch; key.pool_len = f.pool_len;
-    memcpy(key.cam, f.cam, sizeof key.cam);
-    key.width = f.width; key.height = f.height; key.y0 = f.y0; key.y1 = f.y1; key.row_step = f.row_step; key.out_y0 = f.out_y0;
-    key.tiles_y = f.tiles_y;
-    const size_t need = (size_t)f.tiles_y * 8 * (size_t)f.width;   // a record per pixel of the rows the launch writes
-    if (b.kept_valid && memcmp(&key, &b.kept_key, sizeof key) == 0) {
-      if (persist_kept_filled(b)) a.kept = b.kept;
-    } else if ((b.kept_failed == 0 || need < b.kept_failed) && need < (1ull << 30) && persist_kept_idle(b)) {
-      b.kept_valid = false;
-      if (!b.kept_filled && hipEventCreateWithFlags(&b.kept_filled, hipEventDisableTiming) != hipSuccess) {
-        b.kept_filled = nullptr;
-        (void)hipGetLastError();
-      } else if (b.kept_cap < need) {   // (idle, so nothing reads the old buffer; the wait is the one `prim` grows behind)
-        if ((e = hipDeviceSynchronize()) != hipSuccess) return (int)e;
-        if (b.kept) (void)hipFree(b.kept);
-        b.kept = nullptr; b.kept_cap = 0;
-        if (hipMalloc((void **)&b.kept, 3 * need * sizeof(uint4)) == hipSuccess) b.kept_cap = need;
-        else { b.kept = nullptr; b.kept_failed = need; (void)hipGetLastError(); }   // no room: today's kernel, and no error
-      }
-      if (b.kept_filled && b.kept_cap >= need) { a.kept = b.kept; a.kept_fill = 1; b.kept_key = key; }
-    }
-    a.kept_n = (uint32_t)b.kept_cap; a.kept_origin = (uint32_t)f.out_y0 * (uint32_t)f.width;
-  }
-  if (b.head_used[hset] && (e = hipStreamWaitEvent(stream, b.head_done[hset], 0)) != hipSuccess) return (int)e;
-  for (int s = 0; s < (fold > 1 ? 1 : spp); s++) {
-    a.reverse = SVO_SERPENTINE ? (int)(b.launches++ & 1u) : 0;
+  // (one wait for the device, not one per set inside a run; launches in flight may still read the old tables)
+  if (plan.tables && b.rc_floats < plan.rc_floats &&
+      (e = grow_device_buffers(b.rc, nullptr, b.rc_floats, plan.rc_floats, plan.rc_floats * sizeof(float))) != hipSuccess)
+    return (int)e;
+
+  PersistArgs a = persist_args(plan, f, in, b, hset, facc);
+  if (p.set.ntab_mode == 0) a.ntab = nullptr;
+  if (plan.cache && (e = persist_kept_choose(p, in, f, plan.kept_records, a)) != hipSuccess) return (int)e;
+
+  if (b.head_used[hset] && (e = hipStreamWaitEvent(in.stream, b.head_done[hset], 0)) != hipSuccess) return (int)e;
+  const int nb = f.batch > 1 ? f.batch : 1;
+  for (int s = 0; s < plan.launches; s++) {
+    a.reverse = (int)(b.launches++ & 1u);   // serpentine: consecutive launches walk the columns in opposite directions
     a.sample = s;
-    const int nb = f.batch > 1 ? f.batch : 1;
-    const bool packed = a.rc && fvar && fvar_host && nb <= kCamPack;
-    if (fvar && !packed && s == 0 && copy_cams) { const int rcc = copy_cams(copy_arg); if (rcc) return rcc; }
+    const bool packed = a.rc && in.fvar && in.fvar_host && nb <= kCamPack;
+    if (in.fvar && !packed && s == 0 && in.copy_cams) { const int rcc = in.copy_cams(in.copy_arg); if (rcc) return rcc; }
     if (a.rc) {
       FrameVarPack pack;
-      if (packed) memcpy(pack.v, fvar_host, (size_t)nb * sizeof(FrameVar));
+      if (packed) memcpy(pack.v, in.fvar_host, (size_t)nb * sizeof(FrameVar));
       else memset(&pack, 0, sizeof pack);
       const unsigned per_frame = (unsigned)((f.width + f.height + SVO_RC_BLOCK - 1) / SVO_RC_BLOCK);
-      const dim3 tgrid(per_frame < (unsigned)SVO_RC_WAVES ? per_frame : (unsigned)SVO_RC_WAVES, (unsigned)(f.batch > 1 ? f.batch : 1));
-      hipLaunchKernelGGL(rc_table_kernel, tgrid, dim3(SVO_RC_BLOCK), 0, stream, f, fvar, b.rc[hset], a.rc_stride, s, a.heads, pack, packed ? nb : 0);
-      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+      const dim3 tgrid(per_frame < (unsigned)SVO_RC_WAVES ? per_frame : (unsigned)SVO_RC_WAVES, (unsigned)nb);
+      hipLaunchKernelGGL(rc_table_kernel, tgrid, dim3(SVO_RC_BLOCK), 0, in.stream, f, in.fvar, b.rc[hset], a.rc_stride, s, a.heads, pack, packed ? nb : 0);
     } else {
-      hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, stream, a.heads, (uint32_t)kHeadWords);
-      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, in.stream, a.heads, (uint32_t)kHeadWords);
     }
+    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     switch (f.render_mode) {
-      case 0: persist_launch_mode<0>(a, blocks, stream); break;
-      case 1: persist_launch_mode<1>(a, blocks, stream); break;
-      case 2: persist_launch_mode<2>(a, blocks, stream); break;
-      case 3: persist_launch_mode<3>(a, blocks, stream); break;
-      default: persist_launch_mode<4>(a, blocks, stream); break;
+      case 0: persist_launch_mode<0>(a, plan.blocks, in.stream); break;
+      case 1: persist_launch_mode<1>(a, plan.blocks, in.stream); break;
+      case 2: persist_launch_mode<2>(a, plan.blocks, in.stream); break;
+      case 3: persist_launch_mode<3>(a, plan.blocks, in.stream); break;
+      default: persist_launch_mode<4>(a, plan.blocks, in.stream); break;
     }
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   }
-  if ((e = hipEventRecord(b.head_done[hset], stream)) != hipSuccess) return (int)e;
+  if ((e = hipEventRecord(b.head_done[hset], in.stream)) != hipSuccess) return (int)e;
   b.head_used[hset] = true;
-  if (a.kept && a.kept_fill) {
-    if ((e = hipEventRecord(b.kept_filled, stream)) != hipSuccess) return (int)e;
-    b.kept_valid = true; b.kept_fill_inflight = true; b.kept_fills++;
-  } else if (a.kept) {
-    b.kept_reader[hset] = true; b.kept_reuses++;
-  }
+  if ((e = persist_kept_launched(p, a, hset, in.stream)) != hipSuccess) return (int)e;
   if (resolve) {
-    if (sequence) {
-      hipLaunchKernelGGL(persist_resolve_sequence_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y), dim3(64), 0, stream, f, facc, fold, color);
-    } else if (fold > 1) {
-      dim3 grid((unsigned)f.tiles_x, (unsigned)f.tiles_y, (unsigned)(f.batch > 1 ? f.batch : 1));
-      hipLaunchKernelGGL(persist_resolve_tiles_kernel, grid, dim3(64), 0, stream, f, facc, fold, color);
-    } else {
-      dim3 grid((unsigned)((f.width + 255) / 256), (unsigned)(f.tiles_y * 8), (unsigned)(f.batch > 1 ? f.batch : 1));
-      hipLaunchKernelGGL(persist_resolve_kernel, grid, dim3(256), 0, stream, f, facc, npix, color);
-    }
+    persist_resolve(plan, f, in, facc);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    if ((e = hipEventRecord(b.facc_done[fset], stream)) != hipSuccess) return (int)e;
+    if ((e = hipEventRecord(b.facc_done[fset], in.stream)) != hipSuccess) return (int)e;
     b.facc_used[fset] = true;
   }
   return 0;

@@ -153,7 +153,7 @@ inline hipError_t prepare(State &s) {
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    // what a waiting dispatch fills a CU with (persist_launch), and no more than fit of this kernel
+    // what a waiting dispatch fills a CU with (persist_prepare), and no more than fit of this kernel
     int pk = 0, rk = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pk, persist_kernel<0, ByteWalk>, 64, 0) != hipSuccess || pk < 1) pk = 16;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&rk, rays_kernel<ByteWalk>, 64, 0) != hipSuccess || rk < 1) rk = 16;
@@ -167,13 +167,14 @@ inline hipError_t prepare(State &s) {
 }
 
 // Enqueues one cast of a.n rays (> 0) on `stream`: the counter's turn, its zeroing, the launch, the events around it.
-// waves_per_cu <= 0: what a waiting dispatch uses.  a.head is set here.
-inline hipError_t launch(State &s, Args a, bool walk_table, int waves_per_cu, hipStream_t stream) {
+// Waves per CU: the host's figure (svo_set_tuning), else what a waiting dispatch uses -- persist_plan's rule for a launch
+// that has the GPU to itself.  a.head is set here.
+inline hipError_t launch(State &s, Args a, bool walk_table, const PersistSettings &set, hipStream_t stream) {
   hipError_t e;
   const int i = (int)(s.next % kCounters);
   if (s.used[i] && (e = hipStreamWaitEvent(stream, s.e1[i], 0)) != hipSuccess) return e;
   a.head = s.heads + i * kCounterStride;
-  const int per_cu = waves_per_cu > 0 ? waves_per_cu : s.fit[walk_table ? 1 : 0];
+  const int per_cu = persist_waves_per_cu(set, s.fit[walk_table ? 1 : 0]);
   const uint64_t want = ((uint64_t)a.n + 63u) / 64u, room = (uint64_t)per_cu * (uint64_t)s.cus;
   const int waves = (int)std::min(want, room);
   if ((e = hipEventRecord(s.e0[i], stream)) != hipSuccess) return e;

@@ -29,7 +29,7 @@ namespace svo {
 constexpr int kRecWords = 18;                       // words of a path record
 constexpr int kRecWaveWords = 2 * kRecWords * 64;   // two records per lane
 
-// SVO_SPARE_THRESH (svo_persistent.hip.h), sixteenths: a round starts once that share of the lanes is all that still traverses
+// SVO_SPARE_THRESH (svo_persist_plan.h), sixteenths: a round starts once that share of the lanes is all that still traverses
 // -- the others wait without a spare
 
 // SVO_SPARE_RECORDS (svo_persistent.hip.h): where the two path records of a lane live

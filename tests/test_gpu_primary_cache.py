@@ -318,3 +318,27 @@ def test_ineligible_paths_do_not_use_the_cache(ctx):
     after = ctx.primary_cache_info()
     assert after["reuses"] == before["reuses"] == after["reuses"] and after["fills"] == before["fills"], (before, after)
     assert after["state"] == 0
+
+
+def test_settings_and_counts_survive_a_resize(ctx):
+    """svo_resize frees the persistent pipeline's buffers, not what the host set: svo_set_tuning's launch shape, the cache's
+    opt-out and the counts svo_primary_cache_info reports are the same after a resize to another size and back."""
+    _setup(ctx, "terrain", "K1", 64, 64)
+    _frames(ctx, 4, 2, slots=1)                        # a fill and a reuse: the counts are not zero
+    before = ctx.primary_cache_info()
+    assert before["fills"] >= 1 and before["reuses"] >= 1, before
+    ctx.set_tuning(3, 11)
+    ctx.set_primary_cache(False)
+    try:
+        ctx.resize(32, 32)
+        ctx.resize(64, 64)
+        ctx.set_params(FIRST, 0, 0, 0, 2, 0, 1)
+        ctx.dispatch()
+        assert ctx.launch_info() == {"waves": 64, "waves_per_cu": 3, "round_threshold_sixteenths": 11}   # 64 tiles < 3 waves x CUs
+        _frames(ctx, 2, 2, slots=1)                    # a static-camera batch: would fill
+        after = ctx.primary_cache_info()
+        assert after["fills"] == before["fills"] and after["reuses"] == before["reuses"], (before, after)
+        assert after["state"] == 0
+    finally:
+        ctx.set_tuning(0, 0)
+        ctx.set_primary_cache(True)

@@ -804,6 +804,13 @@ int svo_primary_cache_info(svo_ctx *c, uint64_t *fills, uint64_t *reuses, uint64
   return SVO_OK;
 }
 
+int svo_dense_shade_info(svo_ctx *c, uint64_t *launches, uint64_t *bytes) {
+  if (!c) return SVO_E_INVALID;
+  if (launches) *launches = c->pb.set.dense_launches;
+  if (bytes) *bytes = (uint64_t)c->pb.buf.ray_records * kRayBytes * kHeadSets;
+  return SVO_OK;
+}
+
 static int ensure_derived(svo_ctx *c);
 
 int svo_set_derived(svo_ctx *c, int mode) {

@@ -1,6 +1,6 @@
 // svo_persist_plan.h -- what a launch of the persistent pipeline (svo_persistent.hip.h) decides before it touches the GPU:
 // which kernel, how many waves, whether samples fold, whether the batch shares its primary rays, whether tables are made,
-// whether the primary-hit cache is a candidate, and how much room the launch's buffers need.  A pure function of a few
+// whether the primary-hit cache is a candidate, whether its readers shade in a dense pass, and how much room the launch's buffers need.  A pure function of a few
 // integers: no HIP call, no environment, no device type -- a host compiler can include this header on its own
 // (tests/persist_plan_cases.cpp prints the plan of a list of cases).
 #pragma once
@@ -45,9 +45,13 @@ struct PersistSettings {
   int span_mode = 1;      // 1 = a static-camera batch of mode 0 casts its primary rays once (persist_span_kernel); environment
                           // SVO_BATCH_PRIMARY=0: every frame of the batch casts its own
   int kept_mode = 1;      // svo_set_primary_cache
+  int dense_mode = 1;     // 1 = a launch that reads the cache and ends its paths with the bounce shades every (pixel, frame) in a dense
+                          // pass and casts the prepared rays (bounce_rays_kernel + persist_cast_kernel); environment
+                          // SVO_DENSE_SHADE=0: persist_kept_kernel<false> shades in its rounds
   int cus_reserved = 0;   // CUs the launching stream may not use (svo_set_reserved_cus): fewer persistent waves
   uint64_t pool_epoch = 0;   // bumped by everything that changes the pool (svo_hip.hip::pool_changed)
   uint64_t kept_fills = 0, kept_reuses = 0;
+  uint64_t dense_launches = 0;   // launches that took the dense pass (svo_dense_shade_info)
 };
 
 // What the device offers, asked once: CUs, and resident waves per CU of the record walk / the descriptor walk / the spare-ray kernel
@@ -118,7 +122,13 @@ struct PersistPlan {
   size_t prim_waves = 0;    // persistent waves the primary-hit records must have room for (0: not a kSpan launch)
   size_t rc_stride = 0, rc_floats = 0;   // floats of one frame's tables / of the launch's (0: no tables)
   size_t kept_records = 0;  // records per plane of the cache: one per pixel of the rows the launch writes (0: no candidate)
+  // a cache candidate whose paths are primary + one bounce: once the launch READS the cache, everything about a (pixel, frame)
+  // but "did the bounce hit, and at what t" is known before its ray is cast, so the shading runs ahead of the walk in a dense
+  // kernel.  (Longer paths shade their inner hits from the cast's result; every mirror mask is fine: scatter() takes it.)
+  bool dense = false;
+  size_t ray_records = 0;   // ray records the pass writes: one per (pixel of the launch's rows, frame of the batch) (0: no dense pass)
 };
+constexpr size_t kRayBytes = 20;   // a ray record: {direction, rgba8 of a miss} in a 16-byte plane, rgba8 of a hit in a 4-byte plane
 
 // `out_npix` = elements of the output images: W*H, or more when packed stripes overhang the frame (caller-owned gather
 // buffers).  has_table: the launch walks the interior-descriptor table (else the records); has_cams: the frames of the batch
@@ -176,6 +186,8 @@ inline PersistPlan persist_plan(const PersistSettings &s, const PersistLimits &l
   // the primary-hit cache: static-camera batches without hit records (those would need a fourth plane), on the tables' kernels
   p.cache = p.span && s.kept_mode != 0 && f.write_hits == 0 && p.tables;
   if (p.cache) p.kept_records = (size_t)f.tiles_y * 8 * (size_t)f.width;
+  p.dense = p.cache && s.dense_mode != 0 && f.bounces == 2;
+  if (p.dense) p.ray_records = p.kept_records * (size_t)nb;
   return p;
 }
 

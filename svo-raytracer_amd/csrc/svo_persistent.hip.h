@@ -97,14 +97,19 @@ __device__ __forceinline__ uint32_t xcc_id() {
   return x & 7u;
 }
 
+// the live shader's pixel (one sample, no accumulation): the marker in the corner, then rgba8.  Alpha is 255: no such word is 0.
+__device__ __forceinline__ uint32_t persist_rgba8(const Frame &f, int px, int py, V3 col) {
+  if (px < 10 && py < 10) col = f.dword0 == 0u ? mk(1.f, 0.f, 0.f) : mk(1.f, 1.f, 1.f);
+  return unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xff000000u;
+}
+
 // `sk`: sample index (bits 0..15) and frame of the batch (bits 16..23) of this path when the launch carries all samples of
 // its pixels (a.fold > 1), else 0
 __device__ __forceinline__ void persist_emit(const PersistArgs &a, uint32_t pix, uint32_t sk, int px, int py, V3 col, float depth) {
   const uint32_t smp = sk & 0xffffu;
   // (a kernel that stores nothing was a compile-time experiment: the ceiling of any staging scheme, profiles/round4_experiments.txt)
   if (a.f.spp <= 1 && !a.f.progressive) {   // the live shader's case: straight to rgba8
-    if (px < 10 && py < 10) col = a.f.dword0 == 0u ? mk(1.f, 0.f, 0.f) : mk(1.f, 1.f, 1.f);
-    a.color[pix] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xff000000u;
+    a.color[pix] = persist_rgba8(a.f, px, py, col);
   } else if (a.fold > 1) {
     // every sample in a slot of its own, [frame][tile][sample][channel][pixel of the tile]: the 64 values of a tile's
     // sample and channel share two cache lines, and the kernel that adds the samples up in order reads them coalesced
@@ -224,6 +229,8 @@ struct DescWalk {
     return trav_result2(pool, tab, t, status);
 #endif
   }
+  // where a stopped cast stopped, for a caller that reads nothing else of the result: no load (result() fetches the node's record)
+  __device__ __forceinline__ float stop_t(const State &t) const { return t.t_min; }
   __device__ __forceinline__ void run(Stack &stk, uint32_t lane, State &t, int &status, unsigned long long act, int threshold,
                                       unsigned long long cone_lanes, uint32_t *mix) const {
 #if SVO_ASM_LOOP
@@ -703,6 +710,35 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_span_k
   persist_body<0, DescWalk, false, kTab, true>(a, stk);
 }
 
+// The shading of a hit a mode-0 path goes on from, as persist_body's kSpan branch states it -- ONE text for the two places that
+// run it from a kept primary hit: persist_reuse_body in its rounds and bounce_rays_kernel ahead of the walk.  The same operations
+// in the same order (-ffp-contract=off, no fast-math), so the same bits wherever it is inlined.  Two functions because the reuse
+// kernel runs them a traversal apart: shade_hit() when the hit is known -- the new direction, the sums, and `sun_lit`: should the new
+// ray leave the octree, the path ends with scatter() of exactly these values against the sun (kSpanSun) -- and path_end() when the
+// cast has said whether the path's last ray hit.
+__device__ __forceinline__ V3 shade_hit(const Frame &f, V3 d, V3 hpos, V3 hnormal, uint32_t hvalue, float r, V3 &mask, V3 &accum, bool &sun_lit) {
+  const V3 sun = normalize3(mk(1.0f, 1.0f, 1.0f));
+  const bool mirror = ((f.mirror_mask >> (hvalue & 31u)) & 1u) != 0u;
+  const V3 nd = scatter(d, hnormal, r, mirror);
+  const V3 mc = material_colour(hvalue, mk(hpos.x - 1.0f, hpos.y - 1.0f, hpos.z - 1.0f));
+  accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
+  mask = mk(mask.x * mc.x, mask.y * mc.y, mask.z * mc.z);
+  const float k = dot3(nd, hnormal);
+  mask = mk(mask.x * k, mask.y * k, mask.z * k);
+  const V3 nd2 = scatter(nd, hnormal, r, mirror);   // kSpanSun: what a miss of the new ray will add
+  sun_lit = acos_pinned(dot3(nd2, sun)) < 0.4f;
+  return nd;
+}
+__device__ __forceinline__ V3 path_end(V3 accum, V3 mask, bool hit, bool sun_lit) {
+  if (hit) {
+    accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
+  } else {
+    if (sun_lit) accum = mk(accum.x + mask.x * 7.0f, accum.y + mask.y * 7.0f, accum.z + mask.z * 7.0f);
+    accum = mk(accum.x + mask.x * 1.0f, accum.y + mask.y * 1.0f, accum.z + mask.z * 1.0f);
+  }
+  return accum;
+}
+
 // The reuse of the context's primary-hit cache (persist_kept_kernel<false>): the kSpan kernel of a launch whose primary hits an
 // earlier launch of the same camera, pool and frame left in a.kept (the fill).  A refilled lane casts nothing: it loads its
 // pixel's record and shades frame 0 from it exactly as the kSpan kernel shades frames 1.. from its lane's own -- the same
@@ -716,7 +752,6 @@ __device__ __forceinline__ void persist_reuse_body(const PersistArgs &a, DescWal
   const Frame &f = a.f;
   DescWalk walk;
   walk.setup(a);
-  const V3 sun = normalize3(mk(1.0f, 1.0f, 1.0f));
 
   DescWalk::State t;
   int status = ST_IDLE;
@@ -738,15 +773,8 @@ __device__ __forceinline__ void persist_reuse_body(const PersistArgs &a, DescWal
       const Cast c = walk.result(t, status);
       const uint32_t segn = seg & 0xffu;   // (never 0: no lane of this kernel casts a primary ray)
       if (!c.hit || (int)segn + 1 >= f.bounces) {   // frame (seg >> 24)'s path ends
-        float edepth = 0.0f;
-        if (c.hit) {
-          accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
-          edepth = c.t;
-        } else {
-          if ((seg & kSpanSun) != 0u) accum = mk(accum.x + mask.x * 7.0f, accum.y + mask.y * 7.0f, accum.z + mask.z * 7.0f);
-          accum = mk(accum.x + mask.x * 1.0f, accum.y + mask.y * 1.0f, accum.z + mask.z * 1.0f);
-        }
-        persist_emit(a, pix, 0u, px, py, accum, edepth);
+        accum = path_end(accum, mask, c.hit, (seg & kSpanSun) != 0u);
+        persist_emit(a, pix, 0u, px, py, accum, c.hit ? c.t : 0.0f);
         const uint32_t fi = (seg >> 24) + 1u;
         if (fi < (uint32_t)f.batch) {   // keeps its pixel
           seg = fi << 24;
@@ -831,18 +859,11 @@ __device__ __forceinline__ void persist_reuse_body(const PersistArgs &a, DescWal
     // ---------------- one shading pass: a hit the path goes on from (persist_plan: f.bounces >= 2), persist_body's kSpan shading
     bool ninit = false;
     if (shade) {
-      const bool mirror = ((f.mirror_mask >> (hvalue & 31u)) & 1u) != 0u;
-      const V3 nd = scatter(d, hnormal, r, mirror);
-      const V3 mc = material_colour(hvalue, mk(hpos.x - 1.0f, hpos.y - 1.0f, hpos.z - 1.0f));
-      accum = mk(accum.x + mask.x * 0.0f, accum.y + mask.y * 0.0f, accum.z + mask.z * 0.0f);
-      mask = mk(mask.x * mc.x, mask.y * mc.y, mask.z * mc.z);
-      const float k = dot3(nd, hnormal);
-      mask = mk(mask.x * k, mask.y * k, mask.z * k);
-      d = nd;
+      bool sun_lit;
+      d = shade_hit(f, d, hpos, hnormal, hvalue, r, mask, accum, sun_lit);
       seg++;
       ninit = true;
-      const V3 nd2 = scatter(d, hnormal, r, mirror);   // kSpanSun: what a miss of the new ray will add
-      seg = acos_pinned(dot3(nd2, sun)) < 0.4f ? (seg | kSpanSun) : (seg & ~kSpanSun);
+      seg = sun_lit ? (seg | kSpanSun) : (seg & ~kSpanSun);
     }
     // ---------------- set up the new rays
     if (ninit) {
@@ -868,6 +889,165 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_kept_k
   __shared__ DescWalk::Stack stk;
   if constexpr (kFill) persist_body<0, DescWalk, false, true, true, true>(a, stk);
   else persist_reuse_body(a, stk);
+}
+
+// ---------------- the dense pass of a launch that reads the cache and whose paths are primary + one bounce (PersistPlan::dense)
+// With f.bounces == 2 a (pixel, frame)'s path is decided before its bounce ray is cast, but for two facts: did the ray hit, and at
+// what t.  The direction, and the colour of either ending, are functions of the kept record, the row / column tables and the frame
+// number; the hit's record is never read.  So the shading leaves the half-empty persistent waves: bounce_rays_kernel runs it at 64
+// of 64 lanes for every (pixel, frame) and leaves a ray record; persist_cast_kernel only draws, loads, casts and stores.
+
+// The ray records of a launch, [frame of the batch][pixel of the launch's rows, indexed like the cache]: kRayBytes each
+struct RayArgs {
+  uint4 *ray;       // {direction of the bounce ray, rgba8 should it miss}; w == 0 (no pixel's word: alpha is 255) = the pixel's PRIMARY
+                    // ray left the octree: nothing to cast, bounce_rays_kernel has stored the sky
+  uint32_t *hitc;   // rgba8 should it hit.  Not assumed black: a voxel with normal code 0 gives a NaN direction and NaN sums (quirk Q7)
+  uint32_t n;       // records per frame
+};
+
+// One thread per (pixel of the launch's rows, frame of the batch); a workgroup = one wave = an 8 x 8 tile of one frame: the reads of
+// the kept records and of the frame's tables coalesce.  The operations of persist_reuse_body on a refilled lane, in its order.
+__global__ __launch_bounds__(64) void bounce_rays_kernel(const PersistArgs a, const RayArgs ra) {
+  const Frame &f = a.f;
+  const uint32_t l = threadIdx.x, fi = blockIdx.z;
+  const int px = (int)(blockIdx.x * 8u + (l & 7u)), py = frame_gy(f, (int)blockIdx.y, (int)(l >> 3));
+  if (px >= f.width || py >= f.y1 || py >= f.height) return;
+  const uint32_t idx = (uint32_t)frame_oy(f, (int)blockIdx.y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px - a.kept_origin;
+  const uint4 *const rec = a.kept + idx;
+  const uint4 r0 = rec[0], r2 = rec[2u * a.kept_n];
+  const V3 d = mk(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
+  const size_t j = (size_t)fi * ra.n + idx;
+  if (r2.w == kKeptMiss) {   // the same sky in every frame; persist_cast_kernel draws again when it meets the flag
+    const V3 s = sky_colour(d);
+    persist_emit(a, idx + a.kept_origin + fi * f.frame_stride, 0u, px, py, mk(0.0f + s.x, 0.0f + s.y, 0.0f + s.z), 0.0f);
+    ra.ray[j] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  const uint4 r1 = rec[a.kept_n];
+  const V3 hpos = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
+  const V3 hnormal = mk(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z));
+  V3 mask = mk(1.f, 1.f, 1.f), accum = mk(0.f, 0.f, 0.f);
+  const float *fr = a.rc + (size_t)fi * a.rc_stride;
+  const float colx = fr[2 * px], roww = fr[((2 * f.width + 3) & ~3) + 8 * py + 3];
+  const float r = rand_of_dot(((float)px + colx) * 12.9898f + ((float)py + roww) * 78.233f);
+  bool sun_lit;
+  const V3 nd = shade_hit(f, d, hpos, hnormal, r1.w, r, mask, accum, sun_lit);
+  const uint32_t miss_c = persist_rgba8(f, px, py, path_end(accum, mask, false, sun_lit));
+  ra.ray[j] = make_uint4(__float_as_uint(nd.x), __float_as_uint(nd.y), __float_as_uint(nd.z), miss_c);
+  ra.hitc[j] = persist_rgba8(f, px, py, path_end(accum, mask, true, sun_lit));
+}
+
+// persist_reuse_body without its shading: the band walk and the draw (a slot per pixel), the trips, thresh_num and the drain rule are
+// the same; a lane at the start of a frame loads that frame's ray record and the origin (the kept hit's position, plane 1 of the
+// cache), and a stopped lane stores one of the record's two colour words.  Across the trips a lane keeps its walk state, its pixel,
+// its frame and the two words.  A cast that hit the iteration cap counts as a miss, as Cast::hit == false does there.
+__device__ __forceinline__ void persist_cast_body(const PersistArgs &a, const RayArgs &ra, DescWalk::Stack &stk) {
+  const uint32_t lane = threadIdx.x;
+  const Frame &f = a.f;
+  DescWalk walk;
+  walk.setup(a);
+
+  DescWalk::State t;
+  int status = ST_IDLE;
+  uint32_t pix = 0, fi = 0, miss_c = 0, hit_c = 0;   // pix: frame fi's output index
+
+  uint32_t band = xcc_id();
+  int bands_left = 8;
+
+  for (;;) {
+    // ---------------- finished lanes store their pixel and go on to the pixel's next frame
+    bool load = false;
+    if (status >= ST_HIT) {
+      const bool hit = status == ST_HIT;
+      a.color[pix] = hit ? hit_c : miss_c;
+      a.depth[pix] = hit ? walk.stop_t(t) : 0.0f;
+      fi++;
+      if (fi < (uint32_t)f.batch) {   // keeps its pixel
+        pix += f.frame_stride;
+        load = true;
+        status = ST_ACTIVE;
+      } else {
+        status = ST_IDLE;
+      }
+    }
+
+    // ---------------- idle lanes draw pixels (persist_reuse_body's draw), then every lane at the start of a frame loads its ray
+    bool ninit = false;
+    V3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 0.f);
+    for (;;) {
+      bool again = false;   // the band still has slots behind this draw
+      const unsigned long long idle = bands_left > 0 ? __ballot(status == ST_IDLE) : 0ull;
+      if (idle != 0ull) {
+        const uint32_t n = (uint32_t)__builtin_popcountll(idle);
+        const int leader = __builtin_ctzll(idle);
+        const int first_row = (int)band * a.rows_per_band;
+        int band_rows = f.tiles_y - first_row;
+        band_rows = band_rows < 0 ? 0 : (band_rows > a.rows_per_band ? a.rows_per_band : band_rows);
+        const uint32_t band_total = (uint32_t)(band_rows * f.tiles_x) * 64u;
+        uint32_t base = 0;
+        if ((int)lane == leader) base = atomicAdd(a.heads + band * kHeadStride, n);
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+        const uint32_t slot =
+            base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+        if (status == ST_IDLE && slot < band_total) {
+          const uint32_t l = slot & 63u, q = slot >> 6;
+          const int full_band = band_rows == a.rows_per_band ? 0 : 1;
+          int tile_x = (int)udiv_by(q, (uint32_t)band_rows, a.mg_rows[full_band]);
+          const int tile_y = first_row + ((int)q - tile_x * band_rows);
+          if (a.reverse) tile_x = f.tiles_x - 1 - tile_x;
+          const int px = tile_x * 8 + (int)(l & 7u), py = frame_gy(f, tile_y, (int)(l >> 3));
+          if (px < f.width && py < f.y1 && py < f.height) {
+            pix = (uint32_t)frame_oy(f, tile_y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px;
+            fi = 0u;
+            load = true;
+            status = ST_ACTIVE;   // taken
+          }
+        }
+        if (base + n >= band_total) {   // this band is used up: the next one in the next round (work stealing)
+          band = (band + 1u) & 7u;
+          bands_left--;
+        } else {
+          again = true;
+        }
+      }
+      if (load) {
+        const uint32_t idx = pix - fi * f.frame_stride - a.kept_origin;
+        const size_t j = (size_t)fi * ra.n + idx;
+        const uint4 q = ra.ray[j];
+        load = false;
+        if (q.w == 0u) {   // (of a new pixel only) sky: stored already, the lane draws again while the band has slots
+          status = ST_IDLE;
+        } else {
+          const uint4 r1 = a.kept[a.kept_n + idx];
+          miss_c = q.w;
+          hit_c = ra.hitc[j];
+          o = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
+          d = mk(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z));
+          ninit = true;
+        }
+      }
+      if (!again || __ballot(status == ST_IDLE) == 0ull) break;
+    }
+    // ---------------- set up the new rays
+    if (ninit) {
+      status = walk.init(t, o, d, true, 0.0f);
+      walk.fresh_stack(stk, lane);
+    }
+    if (__ballot(status != ST_IDLE) == 0ull) {
+      if (bands_left > 0) continue;
+      break;
+    }
+    // ---------------- traverse until enough lanes have stopped to make a round worthwhile (persist_body)
+    const int active0 = __builtin_popcountll(__ballot(status == ST_ACTIVE));
+    const int drained = (active0 * SVO_DRAIN_NUM) / 16 < active0 - 1 ? (active0 * SVO_DRAIN_NUM) / 16 : (active0 > 0 ? active0 - 1 : 0);
+    const int threshold = __builtin_amdgcn_readfirstlane(bands_left > 0 ? (active0 * a.thresh_num) / 16 : drained);
+    walk.run(stk, lane, t, status, __ballot(status == ST_ACTIVE), threshold, ~0ull, nullptr);
+  }
+}
+
+__global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_cast_kernel(const PersistArgs a, const RayArgs ra) {
+  __shared__ DescWalk::Stack stk;
+  persist_cast_body(a, ra, stk);
 }
 
 // a.fold > 1: tiles per group of a band's walk.  1 / 8 / 64 / 512 / all: 4.47 / 4.49 / 4.47 / 4.41 / 4.20 Grays/s at 64
@@ -914,6 +1094,11 @@ struct PersistBuffers {
   bool kept_fill_inflight = false;   // a fill was launched and kept_filled not yet seen complete
   hipEvent_t kept_filled = nullptr;
   bool kept_reader[kHeadSets] = {};  // the set's head_done is behind a launch that read the cache (or behind one that waited for it)
+  // the ray records of the dense pass (bounce_rays_kernel -> persist_cast_kernel), one buffer per counter set like the tables:
+  // kRayBytes x ray_records each, the 16-byte plane first
+  uint8_t *rays[kHeadSets] = {};
+  size_t ray_records = 0;      // records each has room for
+  size_t rays_failed = 0;      // ... and the size hipMalloc last refused: launches of that size and larger shade in persist_kept_kernel<false>
   int last_thresh = 9, last_blocks = 0, last_per_cu = 0;   // shape of the last launch (svo_launch_info)
   unsigned launches = 0, frames = 0;
 };
@@ -930,6 +1115,7 @@ inline void persist_free(PersistBuffers &b) {
   for (auto &p : b.prec) if (p) (void)hipFree(p);
   for (auto &p : b.rc) if (p) (void)hipFree(p);
   for (auto &p : b.prim) if (p) (void)hipFree(p);
+  for (auto &p : b.rays) if (p) (void)hipFree(p);
   for (auto &f : b.facc) if (f) (void)hipFree(f);
   for (auto &e : b.head_done) if (e) (void)hipEventDestroy(e);
   for (auto &e : b.facc_done) if (e) (void)hipEventDestroy(e);
@@ -1185,6 +1371,7 @@ inline hipError_t persist_prepare(PersistState &p) {
     if (const char *e4 = getenv("SVO_RC_TABLE")) s.table_mode = atoi(e4) != 0 ? 1 : 0;
     if (const char *e5 = getenv("SVO_NORMAL_TABLE")) s.ntab_mode = atoi(e5) != 0 ? 1 : 0;
     if (const char *e6 = getenv("SVO_BATCH_PRIMARY")) s.span_mode = atoi(e6) != 0 ? 1 : 0;
+    if (const char *e7 = getenv("SVO_DENSE_SHADE")) s.dense_mode = atoi(e7) != 0 ? 1 : 0;
 #endif
   }
   return hipSuccess;
@@ -1231,6 +1418,33 @@ inline hipError_t persist_kept_launched(PersistState &p, const PersistArgs &a, i
   } else if (a.kept) {
     b.kept_reader[hset] = true; p.set.kept_reuses++;
   }
+  return hipSuccess;
+}
+
+// Does this launch take the dense pass?  The plan says it may (PersistPlan::dense), persist_kept_choose that it READS the cache; what
+// is left is room for its ray records.  They grow with the FILL, next to the cache itself: the wait for the device and the
+// allocations (8 ms at 1080p x 4 frames) then fall on the submission that casts its primaries anyway, not on the first one that
+// could run without.  An allocation that fails is no error: launches of that size shade in their rounds as before.
+inline hipError_t persist_dense_choose(PersistState &p, const PersistPlan &plan, const PersistArgs &a, int hset, RayArgs &ra) {
+  PersistBuffers &b = p.buf;
+  ra.ray = nullptr; ra.hitc = nullptr; ra.n = 0;
+  if (!plan.dense || !a.kept) return hipSuccess;
+  if (b.ray_records < plan.ray_records) {
+    if (b.rays_failed != 0 && plan.ray_records >= b.rays_failed) return hipSuccess;
+    // (launches in flight may still read the old records: grow_device_buffers waits for the device)
+    const hipError_t e = grow_device_buffers(b.rays, nullptr, b.ray_records, plan.ray_records, plan.ray_records * kRayBytes);
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      for (auto &r : b.rays) { if (r) (void)hipFree(r); r = nullptr; }
+      b.rays_failed = plan.ray_records;
+      return hipSuccess;
+    }
+    if (e != hipSuccess) return e;
+  }
+  if (a.kept_fill) return hipSuccess;
+  ra.ray = (uint4 *)b.rays[hset];
+  ra.hitc = (uint32_t *)(b.rays[hset] + b.ray_records * sizeof(uint4));
+  ra.n = (uint32_t)plan.kept_records;
   return hipSuccess;
 }
 
@@ -1325,6 +1539,8 @@ inline int persist_launch(PersistState &p, const Frame &f, const PersistLaunch &
   PersistArgs a = persist_args(plan, f, in, b, hset, facc);
   if (p.set.ntab_mode == 0) a.ntab = nullptr;
   if (plan.cache && (e = persist_kept_choose(p, in, f, plan.kept_records, a)) != hipSuccess) return (int)e;
+  RayArgs ra;
+  if ((e = persist_dense_choose(p, plan, a, hset, ra)) != hipSuccess) return (int)e;
 
   if (b.head_used[hset] && (e = hipStreamWaitEvent(in.stream, b.head_done[hset], 0)) != hipSuccess) return (int)e;
   const int nb = f.batch > 1 ? f.batch : 1;
@@ -1344,6 +1560,14 @@ inline int persist_launch(PersistState &p, const Frame &f, const PersistLaunch &
       hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, in.stream, a.heads, (uint32_t)kHeadWords);
     }
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (ra.ray) {   // (mode 0, one launch: persist_plan) the tables -> every (pixel, frame)'s shading -> the casts
+      hipLaunchKernelGGL(bounce_rays_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y, (unsigned)nb), dim3(64), 0, in.stream, a, ra);
+      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(persist_cast_kernel, dim3((unsigned)plan.blocks), dim3(64), 0, in.stream, a, ra);
+      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+      p.set.dense_launches++;
+      continue;
+    }
     switch (f.render_mode) {
       case 0: persist_launch_mode<0>(a, plan.blocks, in.stream); break;
       case 1: persist_launch_mode<1>(a, plan.blocks, in.stream); break;

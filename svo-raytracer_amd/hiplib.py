@@ -22,7 +22,7 @@ EXPORTS = [
     "svo_ring_read_depth", "svo_ring_read_hits", "svo_ring_read_pixel", "svo_ring_bind_slot", "svo_ring_device_ptrs",
     "svo_set_reserved_cus", "svo_pool_commit", "svo_ring_forward_slot", "svo_dev_alloc", "svo_dev_free", "svo_dev_read",
     "svo_ipc_export", "svo_ipc_open", "svo_ipc_close", "svo_set_sequence", "svo_ring_submit_cams",
-    "svo_build_from_heightmap16", "svo_launch_info", "svo_set_primary_cache", "svo_primary_cache_info",
+    "svo_build_from_heightmap16", "svo_launch_info", "svo_set_primary_cache", "svo_primary_cache_info", "svo_dense_shade_info",
     "svo_pool_download_range", "svo_brush_sphere", "svo_brush_box", "svo_brush_info", "svo_group_brush_sphere", "svo_group_brush_box",
     "svo_pool_compact", "svo_compact_info", "svo_group_pool_compact",
     "svo_cast_rays", "svo_cast_rays_device", "svo_cast_info",
@@ -130,6 +130,8 @@ def lib(path=None):
         L.svo_set_derived.argtypes = [vp, ci]
         L.svo_set_primary_cache.argtypes = [vp, ci]
         L.svo_primary_cache_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci)]
+        if hasattr(L, "svo_dense_shade_info"):      # (an A/B library built from an older commit, SVO_HIP_LIB, has none)
+            L.svo_dense_shade_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
         L.svo_derived_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(ci), fp]
         L.svo_derived_read.argtypes = [vp, u64, u64, vp, vp]
         L.svo_derived_refresh_info.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64), fp]
@@ -181,6 +183,8 @@ def lib(path=None):
         L.svo_group_ring_read_hits.argtypes = [vp, ci, ci, vp]
         L.svo_group_ring_read_pixel.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp]
         for n in EXPORTS:
+            if n == "svo_dense_shade_info" and not hasattr(L, n):
+                continue
             if n not in ("svo_last_error", "svo_group_last_error", "svo_group_member"):
                 getattr(L, n).restype = ci
         _lib = _libs[path] = L
@@ -537,6 +541,13 @@ class HipContext:
         f, r, b, s = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_int()
         self._chk(self._L.svo_primary_cache_info(self._h, ctypes.byref(f), ctypes.byref(r), ctypes.byref(b), ctypes.byref(s)))
         return {"fills": int(f.value), "reuses": int(r.value), "bytes": int(b.value), "state": int(s.value)}
+
+    def dense_shade_info(self):
+        """launches that shaded their bounce rays in the dense pass ahead of the walk (bounce_rays_kernel + persist_cast_kernel),
+        and the device memory their ray records hold"""
+        n, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self._L.svo_dense_shade_info(self._h, ctypes.byref(n), ctypes.byref(b)))
+        return {"launches": int(n.value), "bytes": int(b.value)}
 
     def set_derived(self, mode):
         """0 = walk the pool's records as the shader does, 1 (default) = walk the interior-descriptor table when the

@@ -65,12 +65,108 @@ struct PersistLimits {
 // n / d by multiply-high with m = ceil(2^32 / d) = (2^32 + e) / d, 0 <= e < d: with n = q d + r the product is
 // q 2^32 + q e + r (2^32 + e) / d, so the high word is q exactly while e (n + d) < 2^32.  That is checked against the largest n
 // the launch can form (tile slots of a band x frames x samples: a 4K batch of 17 frames, or 1080p with 16 samples x 2 frames,
-// is already past it); m = 0 otherwise = a real division (svo_persistent.hip.h::udiv_by).
+// is already past it); m = 0 otherwise = a real division (udiv_by).
 inline uint32_t udiv_magic(uint32_t d, uint64_t n_max) {
   if (d <= 1u) return 0u;
   const uint32_t m = 0xffffffffu / d + 1u;
   const uint64_t e = (uint64_t)m * d - (1ull << 32);
   return e * (n_max + d) < (1ull << 32) ? m : 0u;
+}
+
+// ---------------- the draw of the persistent kernels, its pure half: band -> slots, slot -> tile, tile -> pixel.  Plain integers in,
+// plain integers out, the same text on the device and on the host (tests/persist_draw_cases.cpp walks every slot of a launch
+// through it).  On the device persist_cast_body (svo_persistent.hip.h) decodes its slots with it, a slot per pixel; the
+// kernels at their register limit -- persist_body, persist_reuse_body, the spare-ray kernel -- write the same arithmetic
+// out in their refill ("The dense pass", says what calling it cost them) and share udiv_by only.
+
+// n / d by multiply-high with the reciprocal m of udiv_magic; m = 0: n is past what the reciprocal is exact for = a real division
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline uint32_t udiv_by(uint32_t n, uint32_t d, uint32_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return d <= 1u ? n : (m == 0u ? n / d : __umulhi(n, m));
+#else
+  return d <= 1u ? n : (m == 0u ? n / d : (uint32_t)(((uint64_t)n * m) >> 32));
+#endif
+}
+
+// A band = a strip of whole tile rows, one per XCD, walked column by column: the pixels in flight on an XCD form a compact block
+// of the screen (strip height x a few dozen tile columns) instead of two or three full-width tile rows.
+struct Band {
+  int first_row, rows;   // tile rows of the launch the band holds: rows_per_band of them, fewer in the last band, 0 behind it
+  uint32_t frame;        // pixel slots of the band in one frame
+  uint32_t total;        // slots to draw: over the launch's frames x samples, or (slot_is_pixel) one per pixel with all its frames
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline Band band_of(uint32_t band, int rows_per_band, int tiles_x, int tiles_y, int batch, int fold, bool slot_is_pixel) {
+  Band b;
+  b.first_row = (int)band * rows_per_band;
+  int band_rows = tiles_y - b.first_row;
+  band_rows = band_rows < 0 ? 0 : (band_rows > rows_per_band ? rows_per_band : band_rows);
+  b.rows = band_rows;
+  b.frame = (uint32_t)(band_rows * tiles_x) * 64u;
+  b.total = slot_is_pixel ? b.frame : b.frame * (uint32_t)(batch * fold);
+  return b;
+}
+
+// Slot of a band -> frame of the batch, sample, tile and lane in the tile.  Frames of a batch follow one another inside the band: a
+// wave that runs out of frame k goes on with k + 1; the samples of a pixel (fold > 1) follow one another group by group of `group`
+// tiles: sample 0 of the group's tiles, sample 1 of them, ... -- what is in flight at any time are a few tiles' samples, whose
+// primary rays are the same and whose slots in the sample buffer are neighbours.  The two divisions -- by the band's tile slots per
+// frame and by its tile rows -- are multiply-highs by reciprocals made on the host (mg_tpf, mg_rows: persist_plan).
+struct SlotTile {
+  uint32_t fi, si;       // frame of the batch (0 when a slot is a pixel), sample
+  int tile_x, tile_y;    // tile of the launch
+  uint32_t l;            // pixel of the tile, row-major
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline SlotTile slot_tile(const Band &b, uint32_t slot, int rows_per_band, int tiles_x, int reverse, const uint32_t *mg_rows, const uint32_t *mg_tpf,
+                                 int batch, int fold, int group, bool slot_is_pixel) {
+  SlotTile s;
+  s.l = slot & 63u;
+  const uint32_t per_frame = b.frame * (uint32_t)fold;
+  const uint32_t tiles_pf = per_frame >> 6;   // tile slots of the band per frame
+  const int last = b.rows == rows_per_band ? 0 : 1;   // which reciprocal of a pair: 0 = a full band, 1 = the one that is not
+  s.fi = !slot_is_pixel && batch > 1 ? udiv_by(slot >> 6, tiles_pf, mg_tpf[last]) : 0u;
+  const uint32_t q = (slot - s.fi * per_frame) >> 6;
+  s.si = 0u;
+  int j = (int)q;
+  if (fold > 1) {
+    const uint32_t tiles = b.frame >> 6, g = q / ((uint32_t)group * (uint32_t)fold);
+    const uint32_t first = g * (uint32_t)group;
+    const uint32_t gsize = tiles - first < (uint32_t)group ? tiles - first : (uint32_t)group;
+    const uint32_t r = q - first * (uint32_t)fold;
+    s.si = r / gsize;
+    j = (int)(first + r % gsize);
+  }
+  int tile_x = (int)udiv_by((uint32_t)j, (uint32_t)b.rows, mg_rows[last]);
+  s.tile_y = b.first_row + (j - tile_x * b.rows);
+  if (reverse) tile_x = tiles_x - 1 - tile_x;   // serpentine: this launch ends where the next one starts
+  s.tile_x = tile_x;
+  return s;
+}
+
+// ... -> the pixel and its index in the output images; `inside` = false: the tile overhangs the frame or the launch's rows there
+struct SlotPixel {
+  int px, py;
+  uint32_t pix;
+  bool inside;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline SlotPixel slot_pixel(const Frame &f, const SlotTile &s) {
+  SlotPixel p;
+  p.px = s.tile_x * 8 + (int)(s.l & 7u);
+  p.py = frame_gy(f, s.tile_y, (int)(s.l >> 3));
+  p.inside = p.px < f.width && p.py < f.y1 && p.py < f.height;
+  p.pix = s.fi * f.frame_stride + (uint32_t)frame_oy(f, s.tile_y, (int)(s.l >> 3)) * (uint32_t)f.width + (uint32_t)p.px;
+  return p;
 }
 
 // can `n` samples (or frames of a progressive sequence) per pixel be carried by one launch of `f`?

@@ -85,12 +85,6 @@ struct PersistArgs {
   int kept_fill;        // 1 = this launch writes the cache (persist_kept_kernel<true>), 0 = it reads it
 };
 
-// n / d by multiply-high with the reciprocal m the host made (svo_persist_plan.h::udiv_magic); m = 0: n is past what the
-// reciprocal is exact for = a real division
-__device__ __forceinline__ uint32_t udiv_by(uint32_t n, uint32_t d, uint32_t m) {
-  return d <= 1u ? n : (m == 0u ? n / d : __umulhi(n, m));
-}
-
 __device__ __forceinline__ uint32_t xcc_id() {
   uint32_t x;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
@@ -711,7 +705,8 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_span_k
 }
 
 // The shading of a hit a mode-0 path goes on from, as persist_body's kSpan branch states it -- ONE text for the two places that
-// run it from a kept primary hit: persist_reuse_body in its rounds and bounce_rays_kernel ahead of the walk.  The same operations
+// run it from a kept primary hit: persist_reuse_body in its rounds and bounce_rays_kernel ahead of the walk.  (persist_body's kSpan
+// branch keeps its own statement: called from there, persist_span_kernel<true> spills 16 bytes instead of 8.)  The same operations
 // in the same order (-ffp-contract=off, no fast-math), so the same bits wherever it is inlined.  Two functions because the reuse
 // kernel runs them a traversal apart: shade_hit() when the hit is known -- the new direction, the sums, and `sun_lit`: should the new
 // ray leave the octree, the path ends with scatter() of exactly these values against the sun (kSpanSun) -- and path_end() when the
@@ -980,24 +975,17 @@ __device__ __forceinline__ void persist_cast_body(const PersistArgs &a, const Ra
       if (idle != 0ull) {
         const uint32_t n = (uint32_t)__builtin_popcountll(idle);
         const int leader = __builtin_ctzll(idle);
-        const int first_row = (int)band * a.rows_per_band;
-        int band_rows = f.tiles_y - first_row;
-        band_rows = band_rows < 0 ? 0 : (band_rows > a.rows_per_band ? a.rows_per_band : band_rows);
-        const uint32_t band_total = (uint32_t)(band_rows * f.tiles_x) * 64u;
+        const Band b = band_of(band, a.rows_per_band, f.tiles_x, f.tiles_y, 1, 1, true);   // a slot per pixel (svo_persist_plan.h)
+        const uint32_t band_total = b.total;
         uint32_t base = 0;
         if ((int)lane == leader) base = atomicAdd(a.heads + band * kHeadStride, n);
         base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
         const uint32_t slot =
             base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
         if (status == ST_IDLE && slot < band_total) {
-          const uint32_t l = slot & 63u, q = slot >> 6;
-          const int full_band = band_rows == a.rows_per_band ? 0 : 1;
-          int tile_x = (int)udiv_by(q, (uint32_t)band_rows, a.mg_rows[full_band]);
-          const int tile_y = first_row + ((int)q - tile_x * band_rows);
-          if (a.reverse) tile_x = f.tiles_x - 1 - tile_x;
-          const int px = tile_x * 8 + (int)(l & 7u), py = frame_gy(f, tile_y, (int)(l >> 3));
-          if (px < f.width && py < f.y1 && py < f.height) {
-            pix = (uint32_t)frame_oy(f, tile_y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px;
+          const SlotPixel sp = slot_pixel(f, slot_tile(b, slot, a.rows_per_band, f.tiles_x, a.reverse, a.mg_rows, a.mg_tpf, 1, 1, 1, true));
+          if (sp.inside) {
+            pix = sp.pix;
             fi = 0u;
             load = true;
             status = ST_ACTIVE;   // taken

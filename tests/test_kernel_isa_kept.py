@@ -31,9 +31,9 @@ def code_object(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def instructions(code_object):
-    """{fill (1 / 0): mnemonics of persist_kept_kernel<fill>}"""
+    """{fill (1 / 0): mnemonics of persist_kept_kernel<fill>, "cast": of persist_cast_kernel (the same draw, no shading)}"""
     txt = subprocess.check_output([OBJDUMP, "-d", code_object], text=True)
-    out, name = {0: [], 1: []}, None
+    out, name = {0: [], 1: [], "cast": []}, None
     for line in txt.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
         if m and not m.group(1).startswith("_Z"):
@@ -44,7 +44,9 @@ def instructions(code_object):
             for fill in (0, 1):
                 if "persist_kept_kernelILb%dEE" % fill in name:
                     out[fill].append(line.split()[0])
-    assert out[0] and out[1]
+            if "persist_cast_kernel" in name:
+                out["cast"].append(line.split()[0])
+    assert out[0] and out[1] and out["cast"]
     return out
 
 
@@ -59,12 +61,12 @@ def _metadata(code_object):
             continue
         if m.group(2).isdigit():
             cur[m.group(1)] = int(m.group(2))
-        elif m.group(1) == "name" and "persist_kept_kernel" in m.group(2):
+        elif m.group(1) == "name" and ("persist_kept_kernel" in m.group(2) or "persist_cast_kernel" in m.group(2)):
             out[m.group(2)] = cur
     return out
 
 
-@pytest.mark.parametrize("fill", [0, 1])
+@pytest.mark.parametrize("fill", [0, 1, "cast"])
 def test_kept_kernel_zeroes_a_new_ray_s_stack_column(instructions, fill):
     ins = instructions[fill]
     levels = 2 * ins.count("ds_write2st64_b64") + ins.count("ds_write_b64")
@@ -74,7 +76,7 @@ def test_kept_kernel_zeroes_a_new_ray_s_stack_column(instructions, fill):
 
 def test_kept_kernels_keep_six_waves_per_simd_and_the_stack_as_their_only_lds(code_object):
     meta = _metadata(code_object)
-    assert len(meta) == 2, sorted(meta)
+    assert len(meta) == 3, sorted(meta)
     for name, m in meta.items():
         assert m["vgpr_count"] <= 80 and m["agpr_count"] == 0, (name, m)
         assert m["group_segment_fixed_size"] == 12 * 64 * 8, (name, m)

@@ -19,6 +19,7 @@
 // The CPU statement of the same pass is oracle/svo_oracle.c::svo_oracle_beam (the checker; bit-equal floats).
 #pragma once
 #include "svo_device.h"
+#include "svo_grow.h"
 #include "svo_kernels.h"
 #include "svo_trav.h"
 
@@ -221,5 +222,87 @@ inline int beam_camera_ok(const float *c) {
   const float e2 = ex * ex + (ey * ey + ez * ez), d2 = dx * dx + (dy * dy + dz * dz);
   return d2 > 0.0f && e2 <= 1.0e-8f * d2;
 }
+
+// ---- the host side: what a context keeps for the pass, by lifetime
+namespace beam {
+
+constexpr int kSets = 8;
+
+struct State {
+  // the image size (free_images): one beam image per frame in flight, re-used round-robin behind the event of the frame that read
+  // it last
+  float *img[kSets] = {};
+  bool used[kSets] = {};
+  size_t cap = 0;                   // floats in each
+  // the context (free_state)
+  hipEvent_t done[kSets] = {};
+  unsigned frames = 0;              // frames dispatched with the pass so far
+  uint8_t *live = nullptr;          // which nodes of the pool's top levels a cast can end in or below (beam_live_kernel)
+  // the pool's contents (pool_changed)
+  bool live_valid = false;
+};
+
+inline void free_images(State &s) {
+  for (int i = 0; i < kSets; i++) {
+    if (s.img[i]) (void)hipFree(s.img[i]);
+    s.img[i] = nullptr;
+    s.used[i] = false;
+  }
+  s.cap = 0;
+}
+
+inline void free_state(State &s) {
+  free_images(s);
+  for (auto &e : s.done) if (e) (void)hipEventDestroy(e);
+  if (s.live) (void)hipFree(s.live);
+  s = State();
+}
+
+inline void pool_changed(State &s) { s.live_valid = false; }
+
+// The coarse pass of useBeamOptimization (Main.java:257-266), enqueued in front of the frame's trace kernels: grows the images,
+// marks the live nodes once per pool, waits for the last reader of the image it takes (`set`) and launches the kernel; `f` then
+// names that image.  record() behind the frame's kernels.
+inline hipError_t enqueue(State &s, const uint8_t *pool, uint64_t pool_len, Frame &f, hipStream_t stream, int &set) {
+  hipError_t e;
+  const int bw = (f.width + kBeamBlock - 1) / kBeamBlock, bh = (f.height + kBeamBlock - 1) / kBeamBlock;
+  const size_t need = (size_t)bw * (size_t)bh;
+  if (s.cap < need) {
+    if ((e = grow_device_buffers(s.img, s.used, s.cap, need, need * sizeof(float))) != hipSuccess) return e;
+    for (auto &ev : s.done)
+      if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+  }
+  if (!s.live_valid) {
+    // once per pool: mark the live nodes of the top levels, bottom-up.  The pool only changes while the device is idle
+    // (the mutators synchronise it), so no frame in flight reads the table now; the marking is complete before this call
+    // returns, whichever stream the next dispatch uses.
+    if (!s.live && (e = hipMalloc((void **)&s.live, kBeamLiveBytes)) != hipSuccess) return e;
+    for (int d = kBeamTop; d >= 1; d--) {
+      const unsigned n = 1u << (3 * d);
+      hipLaunchKernelGGL(beam_live_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, pool, (uint32_t)pool_len, d, s.live);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+    s.live_valid = true;
+  }
+  set = (int)(s.frames++ % kSets);
+  if (s.used[set] && (e = hipStreamWaitEvent(stream, s.done[set], 0)) != hipSuccess) return e;
+  BeamArgs a;
+  a.pool = pool; a.live = s.live; a.f = f; a.beam = s.img[set]; a.beam_w = bw; a.beam_h = bh;
+  a.cam_ok = beam_camera_ok(f.cam);
+  hipLaunchKernelGGL(beam_kernel, dim3((unsigned)((bw + 7) / 8), (unsigned)(f.tiles_y * 2)), dim3(64), 0, stream, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  f.use_beam = 1; f.beam_w = bw; f.beam = s.img[set];
+  return hipSuccess;
+}
+
+// the frame that read image `set` is enqueued: the image's next user waits for it
+inline hipError_t record(State &s, int set, hipStream_t stream) {
+  const hipError_t e = hipEventRecord(s.done[set], stream);
+  if (e == hipSuccess) s.used[set] = true;
+  return e;
+}
+
+}  // namespace beam
 
 }  // namespace svo

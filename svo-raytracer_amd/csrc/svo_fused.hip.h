@@ -8,6 +8,8 @@
 #include "svo_device.h"
 #include "svo_kernels.h"
 
+#include <cstring>
+
 namespace svo {
 
 struct PathState {
@@ -298,5 +300,87 @@ __global__ __launch_bounds__(64) void pick_kernel(const uint8_t *__restrict__ po
   __threadfence_system();
   __hip_atomic_store(mail, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+
+// ---- the host side: what a context keeps for the pick.  All of it lives as long as the context (free_state) except `live`, which
+// describes ONE image: cleared (invalidate) by a new image size and by everything else that renders into the current set.
+namespace pick {
+
+struct State {
+  int x = -1, y = -1;          // the pick pixel (svo_set_pick); x < 0: none, read-backs wait
+  bool follow_centre = true;   // follows the image centre (the crosshair, Main.java:139-141) until svo_set_pick names a pixel
+  uint32_t *mail = nullptr;    // kPickSlots x kPickWords words of host memory the device writes
+  hipStream_t stream = nullptr;   // the pick launches' own stream (greatest priority), made on first use
+  uint32_t seq = 0;            // sequence number of the last dispatch that carried the pick
+  uint64_t from_mail = 0, waited = 0;   // svo_read_pixel calls answered from the mail / by waiting for the frame (svo_pick_info)
+  bool live = false;           // the current set's last dispatch carried it, at (live_x, live_y)
+  int live_x = -1, live_y = -1;
+  void invalidate() { live = false; }
+};
+
+inline void free_state(State &p) {
+  if (p.stream) (void)hipStreamDestroy(p.stream);
+  if (p.mail) (void)hipHostFree(p.mail);
+  p = State();
+}
+
+// The pick launch of frame `f` (the caller has found the frame eligible and the pixel inside it): ONE wave on the pick stream, a
+// mail slot of its own per dispatch (kPickSlots of them, round-robin).  The pick is a convenience: a runtime that cannot give it
+// its mail or its stream is no error -- the pick stays not live, and every read-back takes the waiting path.
+inline hipError_t launch(State &p, const uint8_t *pool, const Frame &f) {
+  if (!p.mail) {
+    if (hipHostMalloc((void **)&p.mail, (size_t)kPickSlots * kPickWords * sizeof(uint32_t), hipHostMallocCoherent) != hipSuccess) {
+      p.mail = nullptr;
+      (void)hipGetLastError();
+      return hipSuccess;
+    }
+    memset(p.mail, 0, (size_t)kPickSlots * kPickWords * sizeof(uint32_t));
+  }
+  if (!p.stream) {
+    int lo = 0, hi = 0;   // (hi = the greatest priority = the numerically lowest value)
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) hi = 0;
+    if (hipStreamCreateWithPriority(&p.stream, hipStreamNonBlocking, hi) != hipSuccess &&
+        hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking) != hipSuccess) {
+      p.stream = nullptr;
+      (void)hipGetLastError();
+      return hipSuccess;
+    }
+  }
+  const uint32_t seq = p.seq + 1u == 0u ? 1u : p.seq + 1u;   // (0 = "nothing written yet")
+  uint32_t *mail = p.mail + (size_t)(seq % (uint32_t)kPickSlots) * kPickWords;
+  hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(64), 0, p.stream, pool, f, p.x, p.y, mail, seq);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  p.seq = seq;
+  p.live = true; p.live_x = p.x; p.live_y = p.y;
+  return hipSuccess;
+}
+
+// The mail slot of the last pick launch, polled: its launch has written (or will write) the slot -- no wait for the frame, no copy.
+// `got` = the word arrived and the outputs that were asked for are written ({rgba8, depth bits, hit[4]}); false when the pick
+// stream ran dry without the word: the waiting path answers.
+inline hipError_t poll(State &p, bool &got, void *rgba8, float *depth, void *hit16) {
+  volatile uint32_t *m = p.mail + (size_t)(p.seq % (uint32_t)kPickSlots) * kPickWords;
+  got = false;
+  for (unsigned spin = 0;; spin++) {
+    if (__atomic_load_n((const uint32_t *)m, __ATOMIC_ACQUIRE) == p.seq) { got = true; break; }
+    if ((spin & 255u) == 255u) {
+      const hipError_t q = hipStreamQuery(p.stream);
+      if (q == hipSuccess) { got = __atomic_load_n((const uint32_t *)m, __ATOMIC_ACQUIRE) == p.seq; break; }
+      if (q != hipErrorNotReady) return q;
+    }
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
+  }
+  if (got) {
+    p.from_mail++;
+    if (rgba8) { const uint32_t v = m[1]; memcpy(rgba8, &v, 4); }
+    if (depth) { const uint32_t v = m[2]; memcpy(depth, &v, 4); }
+    if (hit16) { uint32_t h[4] = {m[4], m[5], m[6], m[7]}; memcpy(hit16, h, 16); }
+  }
+  return hipSuccess;
+}
+
+}  // namespace pick
 
 }  // namespace svo

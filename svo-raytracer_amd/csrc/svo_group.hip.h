@@ -314,7 +314,7 @@ int svo_group_ring_create(svo_group *g, int slots, int frames_per_slot, int want
     // RCCL's send / receive kernels need CU slots next to persistent waves that hold theirs for a whole launch: with the
     // RCCL exchange every member's slot streams leave at least one CU per XCD free (what the torch driver does for its
     // gather, bench.py --comm-cus); the peer-copy exchange runs on the SDMA engines and needs none
-    if (exchange == 1 && g->n > 1 && c->reserved_cus < 1) c->reserved_cus = 1;
+    if (exchange == 1 && g->n > 1 && c->ring.reserved_cus < 1) c->ring.reserved_cus = 1;
     int rc = gmember(g, r, ring_create_impl(c, slots, frames_per_slot, want_hits, false));
     if (rc) return rc;
     for (int b = 0; b < slots; b++) {
@@ -333,7 +333,7 @@ int svo_group_ring_create(svo_group *g, int slots, int frames_per_slot, int want
       if (r > 0 && exchange == 0) {
         rc = gmember(g, r, svo_ring_forward_slot(c, b, base, g->gather[(size_t)b] + (uint64_t)r * g->chunk_bytes, g->chunk_bytes, nullptr));
         if (rc) return rc;
-        c->ring[(size_t)b].fwd_dst_device = o->device;
+        c->ring.slots[(size_t)b].fwd_dst_device = o->device;
       }
     }
   }
@@ -378,7 +378,7 @@ static int group_submit(svo_group *g, int frame_number, int nframes, const Frame
                                  g->recv_stream[(size_t)b]), "ncclRecv");
       if (rc == SVO_OK)
         rc = gnccl(g, g->nccl_send(g->local[(size_t)r][(size_t)b], (size_t)g->chunk_bytes, ncclUint8, 0, g->comm[(size_t)r],
-                                   g->m[(size_t)r]->ring[(size_t)b].stream), "ncclSend");
+                                   g->m[(size_t)r]->ring.slots[(size_t)b].stream), "ncclSend");
     }
     const int rc2 = gnccl(g, g->nccl_group_end(), "ncclGroupEnd");
     if (rc) return rc;
@@ -414,7 +414,7 @@ int svo_group_ring_wait(svo_group *g, int slot) {
   if (!g->slot_used[(size_t)slot]) return SVO_OK;
   for (int r = 0; r < g->n; r++) {
     svo_ctx *c = g->m[(size_t)r];
-    svo_ctx::RingSlot &s = c->ring[(size_t)slot];
+    RingSlot &s = c->ring.slots[(size_t)slot];
     GHIP(g, hipSetDevice(c->device));
     GHIP(g, hipEventSynchronize(s.e1));
     if (s.fwd_dst && s.e2) GHIP(g, hipEventSynchronize(s.e2));
@@ -433,7 +433,7 @@ int svo_group_ring_query(svo_group *g, int slot, int *done, int *first_frame, in
   float ms_max = 0.0f;
   for (int r = 0; r < g->n && g->slot_used[(size_t)slot]; r++) {
     svo_ctx *c = g->m[(size_t)r];
-    svo_ctx::RingSlot &s = c->ring[(size_t)slot];
+    RingSlot &s = c->ring.slots[(size_t)slot];
     GHIP(g, hipSetDevice(c->device));
     hipError_t q = hipEventQuery((s.fwd_dst && s.e2) ? s.e2 : s.e1);
     if (q == hipErrorNotReady) { fin = false; continue; }

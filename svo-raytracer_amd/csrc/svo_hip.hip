@@ -42,6 +42,24 @@ static_assert(sizeof(svo_hit) == 16, "svo_hit must be 16 bytes");
 // The three output planes of a frame (or of a slot's frames): all allocated, or none (alloc_planes).
 struct Planes { uint32_t *color = nullptr; float *depth = nullptr; uint4 *hits = nullptr; };
 
+static void free_planes(Planes &p) {
+  if (p.color) (void)hipFree(p.color);
+  if (p.depth) (void)hipFree(p.depth);
+  if (p.hits) (void)hipFree(p.hits);
+  p = Planes();
+}
+
+// n_elems elements per plane, all planes or none: `out` is written only when every allocation succeeded
+static hipError_t alloc_planes(size_t n_elems, bool want_hits, Planes &out) {
+  Planes p;
+  hipError_t e = hipMalloc((void **)&p.color, n_elems * 4);
+  if (e == hipSuccess) e = hipMalloc((void **)&p.depth, n_elems * 4);
+  if (e == hipSuccess && want_hits) e = hipMalloc((void **)&p.hits, n_elems * 16);
+  if (e == hipSuccess) out = p;
+  else free_planes(p);
+  return e;
+}
+
 // One {stream, images} set of the library's own (svo_dispatch_async takes turns on them)
 struct ImageSet : Planes {
   hipStream_t stream = nullptr;
@@ -49,6 +67,78 @@ struct ImageSet : Planes {
   bool used = false;           // frame is complete -- at most `overlap` frames are queued
 };
 
+// svo_dispatch_async takes turns on `overlap` sets {stream, images} while the library owns them (the reference's loop, Main.java:132-146,
+// 257-289: frame N + 1 starts in frame N's tail).  Set 0's stream is the context's own: made with it and kept for its lifetime, and
+// its planes are the ones svo_resize makes.  The other sets' streams and planes, and every `done` event, are made on first use
+// (take_next); the planes go with every svo_resize (free_images), the streams and events with the context (free_state).
+// The context's stream / d_* always name ONE set, the one of the last dispatch, so every read-back sees the last dispatched frame.
+struct ImageSets {
+  static constexpr int kMax = 8;
+  ImageSet set[kMax];
+  int cur = 0;
+  int overlap = 4;                // sets svo_dispatch_async takes turns on (svo_set_overlap; 1 = no alternation)
+  bool others_inflight = false;   // a set that is not current may still have a frame in flight
+  ImageSet &operator[](int i) { return set[i]; }
+  ImageSet &current() { return set[cur]; }
+  bool is_own_stream(hipStream_t st) const {
+    for (const ImageSet &s : set) if (s.stream && st == s.stream) return true;
+    return false;
+  }
+  // waits for the frames in flight on every set's stream
+  hipError_t sync_own_streams() {
+    for (ImageSet &s : set)
+      if (s.stream) { const hipError_t e = hipStreamSynchronize(s.stream); if (e != hipSuccess) return e; }
+    others_inflight = false;
+    return hipSuccess;
+  }
+  // The next set in turn, for a frame of n pixels, made whole before it is named: its stream, its zeroed planes, its event, and its
+  // previous frame complete -- the host runs ahead of the GPU by at most `overlap` frames (a swap chain's depth; the pick launches
+  // do not throttle it any more: they need a wave slot, not the frame's turn).  A failed step leaves `cur` as it was, and the next
+  // call tries again.
+  hipError_t take_next(size_t n) {
+    const int k = (cur + 1) % overlap;
+    ImageSet &s = set[k];
+    hipError_t e;
+    if (!s.stream && (e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess) return e;
+    if (!s.color) {
+      if ((e = alloc_planes(n, true, s)) != hipSuccess) return e;
+      if ((e = hipMemsetAsync(s.color, 0, n * 4, s.stream)) != hipSuccess) return e;
+      if ((e = hipMemsetAsync(s.depth, 0, n * 4, s.stream)) != hipSuccess) return e;
+      if ((e = hipMemsetAsync(s.hits, 0, n * 16, s.stream)) != hipSuccess) return e;
+    }
+    if (!s.done && (e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming)) != hipSuccess) return e;
+    if (s.used && (e = hipEventSynchronize(s.done)) != hipSuccess) return e;
+    cur = k;
+    others_inflight = true;
+    return hipSuccess;
+  }
+  // the image size ends: every set's planes go and set 0 is current again; `stream` (the context's) follows if it named a set
+  void free_images(hipStream_t &stream) {
+    for (ImageSet &s : set) { free_planes(s); s.used = false; }
+    if (cur != 0 && (is_own_stream(stream) || stream == nullptr)) stream = set[0].stream;
+    cur = 0; others_inflight = false;
+  }
+  // the context ends (behind free_images)
+  void free_state() {
+    for (ImageSet &s : set) {
+      if (s.done) (void)hipEventDestroy(s.done);
+      if (s.stream) (void)hipStreamDestroy(s.stream);
+      s = ImageSet();
+    }
+  }
+};
+
+#include "svo_ring.hip.h"   // RingSlot, Ring (its functions: further down)
+
+// What a context keeps, by the three lifetimes its state has.  Each lifetime ends in ONE function below, which has one line per
+// feature, all three in the same order (beam, pick, sets, ring, persist, derive, brush, compact, rays):
+//   the context         svo_destroy     beam::State (events, live table), pick::State, ImageSets (streams, events), Ring::reserved_cus,
+//                                       PersistSettings / PersistLimits, derive::Table, brush::State, compact::State, rays::State
+//   the image size      free_outputs    beam::State (images), pick::State::live, ImageSets (planes), Ring (the slots), PersistBuffers
+//                       (svo_resize)    [+ WavefrontBuffers in a variants build]
+//   the pool's contents pool_changed    beam::State::live_valid, derived_valid, PersistSettings::pool_epoch + the primary-hit cache's key
+// A feature that gains a buffer puts it into its own struct and frees it in that struct's function for the lifetime; a new feature
+// adds its line to the functions whose lifetimes it has.
 struct svo_ctx {
   int device = 0;
   hipStream_t stream = nullptr;       // the stream dispatches go to: the current set's, or the caller's (svo_set_stream)
@@ -74,76 +164,27 @@ struct svo_ctx {
   float *d_depth = nullptr;
   uint4 *d_hits = nullptr;
   bool external_outputs = false;
-  // svo_dispatch_async takes turns on `overlap` sets {stream, images} while the library owns them (the reference's loop, Main.java:132-146,
-  // 257-289: frame N + 1 starts in frame N's tail).  Set 0's stream is the context's own: made with it and kept for its lifetime, and
-  // its planes are the ones svo_resize makes.  The other sets' streams and planes, and every `done` event, are made on first use; the
-  // planes go with every svo_resize (free_outputs), the streams and events stay.
-  // c->stream / c->d_* always name ONE set, the one of the last dispatch, so every read-back sees the last dispatched frame.
-  static constexpr int kMaxSets = 8;
-  ImageSet sets[kMaxSets];
-  int cur_set = 0;
-  int overlap = 4;             // image sets svo_dispatch_async takes turns on (svo_set_overlap; 1 = no alternation)
-  bool others_inflight = false;   // a set that is not current may still have a frame in flight
-  bool is_own_stream(hipStream_t st) const {
-    for (const ImageSet &s : sets) if (s.stream && st == s.stream) return true;
-    return false;
-  }
-  // the pick pixel (svo_set_pick): answered from pinned host memory, written by a one-wave launch of its own (launch_pick)
-  int pick_x = -1, pick_y = -1;
-  bool pick_default = true;    // follows the image centre (the crosshair, Main.java:139-141) until svo_set_pick names a pixel
-  uint32_t *pick_mail = nullptr;   // kPickSlots x kPickWords words of host memory the device writes
-  hipStream_t pick_stream = nullptr;   // the pick launches' own stream (greatest priority), made on first use
-  uint32_t pick_seq = 0;       // sequence number of the last dispatch that carried the pick
-  uint64_t pick_from_mail = 0, pick_waited = 0;   // svo_read_pixel calls answered from the mail / by waiting for the frame (svo_pick_info)
-  bool pick_live = false;      // the current set's last dispatch carried it (cleared by everything else that renders into the set)
-  int pick_live_x = -1, pick_live_y = -1;
   DeviceCounters *d_counters = nullptr;
   float4 *d_ntab = nullptr;   // unit normal of every 16-bit normal code (svo_trav2.h::normal_table_kernel), made with the context
-  // beam images: one per frame in flight, re-used round-robin behind the event of the frame that read it last
-  static constexpr int kBeamSets = 8;
-  float *d_beam[kBeamSets] = {};
-  hipEvent_t beam_done[kBeamSets] = {};
-  bool beam_used[kBeamSets] = {};
-  size_t beam_cap = 0;
-  unsigned beam_frames = 0;
-  uint8_t *d_beam_live = nullptr;   // which nodes of the pool's top levels a cast can end in or below (svo_beam.hip.h)
-  bool beam_live_valid = false;     // cleared by everything that changes the pool
+  // the features' state, in the order of the lifetime functions
+  beam::State beam;           // the beam pre-pass: images, their events, the live-node table of the pool (svo_beam.hip.h)
+  pick::State pick;           // the pick pixel (svo_set_pick): answered from pinned host memory a one-wave launch writes (svo_fused.hip.h)
+  ImageSets sets;             // the {stream, images} sets of svo_dispatch_async
+  Ring ring;                  // frames in flight behind the boundary (svo_ring_*, svo_ring.hip.h)
+  PersistState pb;            // the persistent pipeline: settings (they outlive svo_resize), device limits, per-size buffers
+#if SVO_VARIANTS
+  WavefrontBuffers wf;
+#endif
   // interior-descriptor table of the pool (svo_derive.hip.h): rebuilt lazily after every pool change, walked by the
   // persistent pipeline when the pool is derivable
   derive::Table dt;
   bool derived_valid = false;     // cleared by everything that changes the pool
   int derived_mode = 1;           // 0 = always walk the records, 1 = walk the table when there is one
-#if SVO_VARIANTS
-  WavefrontBuffers wf;
-#endif
-  PersistState pb;            // the persistent pipeline: settings (they outlive svo_resize), device limits, per-size buffers
   brush::State bs;             // work items and counters of svo_brush_* (made at the first stroke), what the last stroke did
   compact::State cs;           // events of svo_pool_compact (made at the first call), what the last call did
   rays::State rs;              // counters, staging buffers and counts of svo_cast_rays* (made at the first call)
-  // frames in flight behind the boundary (svo_ring_*): per slot a stream of its own, output buffers for up to
-  // ring_frames consecutive frames, and the events around its last submission
-  struct RingSlot : Planes {        // (the planes: library-owned images, frame after frame)
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipEvent_t e2 = nullptr;      // behind the forward copy of the last submission (svo_ring_forward_slot), made on demand
-    void *xcolor = nullptr, *xdepth = nullptr, *xhits = nullptr; uint64_t xstride = 0;   // caller-owned (svo_ring_bind_slot)
-    int first_frame = 0, nframes = 0;
-    bool used = false;
-    FrameVar *d_fvar = nullptr;   // per-frame cameras of the slot's last submission (svo_ring_submit_cams) ...
-    FrameVar *h_fvar = nullptr;   // ... their pinned staging copy, and the event behind the copy that last read it
-    hipEvent_t fvar_copied = nullptr;
-    // svo_ring_forward_slot: after every submission, src -> dst (a peer's memory) and the submission's number -> *fwd_flag
-    const void *fwd_src = nullptr; void *fwd_dst = nullptr; uint64_t fwd_bytes = 0; void *fwd_flag = nullptr;
-    int fwd_dst_device = -1;      // >= 0: dst lives on that device of THIS process (svo_group_*): a peer copy
-    uint32_t *seq_word = nullptr;
-  };
   std::vector<void *> ipc_opened;
   std::vector<void *> dev_allocs;   // svo_dev_alloc, freed with the context at the latest
-  std::vector<RingSlot> ring;
-  int reserved_cus = 0;        // CUs per XCD the ring's streams leave free (svo_set_reserved_cus)
-  int ring_frames = 0;
-  uint64_t ring_stride = 0;    // elements between consecutive frames of a library-owned slot
-  unsigned ring_next = 0;
   svo_stats stats{};
   std::string err;
 };
@@ -161,7 +202,7 @@ static int fail(svo_ctx *c, int code, const std::string &msg) {
 
 static constexpr uint64_t kPad = 64;  // zero bytes kept behind the pool (8-byte record loads may overhang)
 
-// Where one launch goes and which frames it renders.  make_frame, launch_beam, launch_frame, launch_frame_kernels and launch_pick
+// Where one launch goes and which frames it renders.  make_frame, launch_frame, launch_frame_kernels and launch_pick
 // read these from here and everything else (render mode, bounces, spp, rows and stripes, pipeline, ...) from the context.
 struct Target {
   hipStream_t stream = nullptr;
@@ -172,7 +213,7 @@ struct Target {
   int frame_number = 0;
   float cam[15] = {};
   const FrameVar *cams = nullptr;         // per-frame cameras / frame numbers of the batch (svo_ring_submit_cams), on the host, ...
-  svo_ctx::RingSlot *cams_slot = nullptr; // ... and the slot that keeps them on the device (d_fvar) and stages the copy (ring_copy_cams)
+  RingSlot *cams_slot = nullptr;          // ... and the slot that keeps them on the device (d_fvar) and stages the copy (ring_copy_cams)
   LaunchShape shape = kPlain;                              // the persistent launch's shape unless svo_set_tuning named one
   int overlap_sets = 0;                                    // kOverlap: the number of sets taking turns
 };
@@ -186,38 +227,30 @@ static Target current_target(const svo_ctx *c) {
   return t;
 }
 
-static void free_planes(Planes &p) {
-  if (p.color) (void)hipFree(p.color);
-  if (p.depth) (void)hipFree(p.depth);
-  if (p.hits) (void)hipFree(p.hits);
-  p = Planes();
-}
-
-// n_elems elements per plane, all planes or none: `out` is written only when every allocation succeeded
-static hipError_t alloc_planes(size_t n_elems, bool want_hits, Planes &out) {
-  Planes p;
-  hipError_t e = hipMalloc((void **)&p.color, n_elems * 4);
-  if (e == hipSuccess) e = hipMalloc((void **)&p.depth, n_elems * 4);
-  if (e == hipSuccess && want_hits) e = hipMalloc((void **)&p.hits, n_elems * 16);
-  if (e == hipSuccess) out = p;
-  else free_planes(p);
-  return e;
-}
-
-// every pool mutator starts here, before its argument checks: the pool is about to change (or to be handed out for writing), so
-// what was derived from it no longer describes it
+// The pool's contents end.  Every pool mutator starts here, before its argument checks: the pool is about to change (or to be
+// handed out for writing), so what was derived from it no longer describes it.  (pick, sets, ring, brush, compact and rays keep
+// nothing that describes the pool.)
 static void pool_changed(svo_ctx *c) {
-  if (c) {
-    c->beam_live_valid = false; c->derived_valid = false;
-    c->pb.set.pool_epoch++; persist_kept_drop(c->pb.buf);   // the primary-hit cache: part of its key, and empty from here on
-  }
+  if (!c) return;
+  beam::pool_changed(c->beam);      // the live-node table
+  persist_pool_changed(c->pb);      // the primary-hit cache: part of its key, and empty from here on
+  c->derived_valid = false;         // the descriptor table: rebuilt (or refreshed, svo_pool_update) before the next cast
 }
 
-// waits for the frames in flight on every set's stream
-static int sync_own_streams(svo_ctx *c) {
-  for (ImageSet &s : c->sets) if (s.stream) HIPCHK(c, hipStreamSynchronize(s.stream));
-  c->others_inflight = false;
-  return SVO_OK;
+static void ring_free(svo_ctx *c);   // svo_ring.hip.h
+
+// The image size ends (svo_resize; the context's end goes through here first).  The device is idle.  (derive, brush, compact and
+// rays keep nothing of the image's size.)
+static void free_outputs(svo_ctx *c) {
+  beam::free_images(c->beam);
+  c->pick.invalidate();
+  c->sets.free_images(c->stream);   // (the streams and the events stay)
+  ring_free(c);                     // the ring's images have the size of the frame
+  persist_free(c->pb.buf);
+#if SVO_VARIANTS
+  wavefront_free(c->wf);
+#endif
+  if (!c->external_outputs) { c->d_color = nullptr; c->d_depth = nullptr; c->d_hits = nullptr; }
 }
 
 extern "C" {
@@ -250,66 +283,27 @@ int svo_create(int device, svo_ctx **out) {
   return SVO_OK;
 }
 
-static void ring_free(svo_ctx *c) {
-  for (auto &s : c->ring) {
-    free_planes(s);
-    if (s.e0) (void)hipEventDestroy(s.e0);
-    if (s.e1) (void)hipEventDestroy(s.e1);
-    if (s.e2) (void)hipEventDestroy(s.e2);
-    if (s.seq_word) (void)hipFree(s.seq_word);
-    if (s.d_fvar) (void)hipFree(s.d_fvar);
-    if (s.h_fvar) (void)hipHostFree(s.h_fvar);
-    if (s.fvar_copied) (void)hipEventDestroy(s.fvar_copied);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-  }
-  c->ring.clear();
-  c->pb.set.cus_reserved = 0;
-  c->ring_frames = 0; c->ring_stride = 0; c->ring_next = 0;
-}
-
-static void free_outputs(svo_ctx *c) {
-  ring_free(c);   // the ring's images have the size of the frame
-  for (ImageSet &s : c->sets) { free_planes(s); s.used = false; }   // (the streams and the events stay)
-  if (c->cur_set != 0 && (c->is_own_stream(c->stream) || c->stream == nullptr)) c->stream = c->sets[0].stream;
-  c->cur_set = 0; c->others_inflight = false; c->pick_live = false;
-  if (!c->external_outputs) { c->d_color = nullptr; c->d_depth = nullptr; c->d_hits = nullptr; }
-#if SVO_VARIANTS
-  wavefront_free(c->wf);
-#endif
-  persist_free(c->pb.buf);
-  for (int i = 0; i < svo_ctx::kBeamSets; i++) {
-    if (c->d_beam[i]) (void)hipFree(c->d_beam[i]);
-    c->d_beam[i] = nullptr;
-    c->beam_used[i] = false;
-  }
-  c->beam_cap = 0;
-}
-
+// The context ends: what free_outputs leaves of every feature, then what belongs to no feature.
 int svo_destroy(svo_ctx *c) {
   if (!c) return SVO_E_INVALID;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   free_outputs(c);
-  if (c->d_pool) (void)hipFree(c->d_pool);
-  if (c->d_counters) (void)hipFree(c->d_counters);
-  if (c->d_ntab) (void)hipFree(c->d_ntab);
-  for (auto &e : c->beam_done) if (e) (void)hipEventDestroy(e);
-  if (c->d_beam_live) (void)hipFree(c->d_beam_live);
+  beam::free_state(c->beam);
+  pick::free_state(c->pick);
+  c->sets.free_state();
+  // (ring, persist: settings and counts only, nothing to free)
   derive::free_table(c->dt);
   brush::free_state(c->bs);
   compact::free_state(c->cs);
   rays::free_state(c->rs);
+  if (c->d_pool) (void)hipFree(c->d_pool);
+  if (c->d_counters) (void)hipFree(c->d_counters);
+  if (c->d_ntab) (void)hipFree(c->d_ntab);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
-  ring_free(c);
   for (void *p : c->ipc_opened) if (p) (void)hipIpcCloseMemHandle(p);
   for (void *p : c->dev_allocs) if (p) (void)hipFree(p);
-  if (c->pick_stream) (void)hipStreamDestroy(c->pick_stream);
-  if (c->pick_mail) (void)hipHostFree(c->pick_mail);
-  for (ImageSet &s : c->sets) {
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-  }
   delete c;
   return SVO_OK;
 }
@@ -717,8 +711,8 @@ int svo_resize(svo_ctx *c, int width, int height) {
   HIPCHK(c, hipDeviceSynchronize());
   if (!c->external_outputs) { c->d_color = own.color; c->d_depth = own.depth; c->d_hits = own.hits; }
   c->width = width; c->height = height;
-  if (c->pick_default) { c->pick_x = width / 2; c->pick_y = height / 2; }   // the crosshair: Main.java:139-141 reads (WIDTH / 2, HEIGHT / 2)
-  else if (c->pick_x >= width || c->pick_y >= height) { c->pick_x = -1; c->pick_y = -1; }
+  if (c->pick.follow_centre) { c->pick.x = width / 2; c->pick.y = height / 2; }   // the crosshair: Main.java:139-141 reads (WIDTH / 2, HEIGHT / 2)
+  else if (c->pick.x >= width || c->pick.y >= height) { c->pick.x = -1; c->pick.y = -1; }
   c->y0 = 0; c->y1 = height; c->rows_set = false;  // a new image size resets the row band to the whole frame
   c->row_step = 1; c->out_y0 = 0; c->n_tile_rows = -1;
   return SVO_OK;
@@ -726,10 +720,10 @@ int svo_resize(svo_ctx *c, int width, int height) {
 
 int svo_bind_outputs(svo_ctx *c, void *color, void *depth, void *hits) {
   if (!c) return SVO_E_INVALID;
-  c->pick_live = false;
+  c->pick.invalidate();
   if (!color) {
     c->external_outputs = false;
-    const ImageSet &s = c->sets[c->cur_set];   // (a set is current only once it has its planes)
+    const ImageSet &s = c->sets.current();   // (a set is current only once it has its planes)
     c->d_color = s.color; c->d_depth = s.depth; c->d_hits = s.hits;
     return SVO_OK;
   }
@@ -893,40 +887,37 @@ int svo_set_stream(svo_ctx *c, void *hip_stream) {
   if (hip_stream) {
     // leaving the library's own streams: what they still have in flight writes the library's images, which dispatches on the
     // caller's stream may render into next
-    if (c->others_inflight || c->is_own_stream(c->stream)) {
-      int rc = sync_own_streams(c);
-      if (rc) return rc;
-    }
+    if (c->sets.others_inflight || c->sets.is_own_stream(c->stream)) HIPCHK(c, c->sets.sync_own_streams());
     c->stream = (hipStream_t)hip_stream;
   } else {
-    c->stream = c->sets[c->cur_set].stream;
+    c->stream = c->sets.current().stream;
   }
-  c->pick_live = false;
+  c->pick.invalidate();
   return SVO_OK;
 }
 
 int svo_set_overlap(svo_ctx *c, int sets) {
   if (!c) return SVO_E_INVALID;
-  // 0: one set (no alternation); 1: the default number of sets; 2 .. kMaxSets (8): that many
-  if (sets < 0 || sets > svo_ctx::kMaxSets) return fail(c, SVO_E_INVALID, "svo_set_overlap: 0 (off), 1 (the default number of sets) or 2 .. 8 sets");
-  c->overlap = sets == 0 ? 1 : (sets == 1 ? 4 : sets);
+  // 0: one set (no alternation); 1: the default number of sets; 2 .. ImageSets::kMax (8): that many
+  if (sets < 0 || sets > ImageSets::kMax) return fail(c, SVO_E_INVALID, "svo_set_overlap: 0 (off), 1 (the default number of sets) or 2 .. 8 sets");
+  c->sets.overlap = sets == 0 ? 1 : (sets == 1 ? 4 : sets);
   return SVO_OK;
 }
 
 int svo_pick_info(svo_ctx *c, int *x, int *y, uint64_t *from_mail, uint64_t *waited) {
   if (!c) return SVO_E_INVALID;
-  if (x) *x = c->pick_x;
-  if (y) *y = c->pick_y;
-  if (from_mail) *from_mail = c->pick_from_mail;
-  if (waited) *waited = c->pick_waited;
+  if (x) *x = c->pick.x;
+  if (y) *y = c->pick.y;
+  if (from_mail) *from_mail = c->pick.from_mail;
+  if (waited) *waited = c->pick.waited;
   return SVO_OK;
 }
 
 int svo_set_pick(svo_ctx *c, int x, int y) {
   if (!c) return SVO_E_INVALID;
-  if (x < 0 || y < 0) { c->pick_x = -1; c->pick_y = -1; c->pick_default = false; return SVO_OK; }   // no pick: read-backs wait
+  if (x < 0 || y < 0) { c->pick.x = -1; c->pick.y = -1; c->pick.follow_centre = false; return SVO_OK; }   // no pick: read-backs wait
   if (c->width > 0 && (x >= c->width || y >= c->height)) return fail(c, SVO_E_INVALID, "svo_set_pick: outside the image");
-  c->pick_x = x; c->pick_y = y; c->pick_default = false;
+  c->pick.x = x; c->pick.y = y; c->pick.follow_centre = false;
   return SVO_OK;
 }
 
@@ -979,39 +970,6 @@ static size_t out_elems(const svo_ctx *c, const Frame &f) {
   return std::max((size_t)c->width * (size_t)c->height, (size_t)(f.out_y0 + f.tiles_y * 8) * (size_t)c->width);
 }
 
-// the coarse pass of useBeamOptimization (Main.java:257-266), enqueued in front of the frame's trace kernels
-static int launch_beam(svo_ctx *c, const Target &t, Frame &f, int &set) {
-  const int bw = (f.width + kBeamBlock - 1) / kBeamBlock, bh = (f.height + kBeamBlock - 1) / kBeamBlock;
-  const size_t need = (size_t)bw * (size_t)bh;
-  if (c->beam_cap < need) {
-    HIPCHK(c, grow_device_buffers(c->d_beam, c->beam_used, c->beam_cap, need, need * sizeof(float)));
-    for (auto &ev : c->beam_done) if (!ev) HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  }
-  if (!c->beam_live_valid) {
-    // once per pool: mark the live nodes of the top levels, bottom-up.  The pool only changes while the device is idle
-    // (the mutators synchronise it), so no frame in flight reads the table now; the marking is complete before this call
-    // returns, whichever stream the next dispatch uses.
-    if (!c->d_beam_live) HIPCHK(c, hipMalloc((void **)&c->d_beam_live, kBeamLiveBytes));
-    for (int d = kBeamTop; d >= 1; d--) {
-      const unsigned n = 1u << (3 * d);
-      hipLaunchKernelGGL(beam_live_kernel, dim3((n + 255) / 256), dim3(256), 0, t.stream, c->d_pool, (uint32_t)c->pool_len, d,
-                         c->d_beam_live);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(t.stream));
-    c->beam_live_valid = true;
-  }
-  set = (int)(c->beam_frames++ % svo_ctx::kBeamSets);
-  if (c->beam_used[set]) HIPCHK(c, hipStreamWaitEvent(t.stream, c->beam_done[set], 0));
-  BeamArgs a;
-  a.pool = c->d_pool; a.live = c->d_beam_live; a.f = f; a.beam = c->d_beam[set]; a.beam_w = bw; a.beam_h = bh;
-  a.cam_ok = beam_camera_ok(f.cam);
-  hipLaunchKernelGGL(beam_kernel, dim3((unsigned)((bw + 7) / 8), (unsigned)(f.tiles_y * 2)), dim3(64), 0, t.stream, a);
-  HIPCHK(c, hipGetLastError());
-  f.use_beam = 1; f.beam_w = bw; f.beam = c->d_beam[set];
-  return SVO_OK;
-}
-
 static int launch_frame_kernels(svo_ctx *c, const Target &t, Frame &f, bool count, uint32_t *color, float *depth, uint4 *hits);
 
 // The descriptor table follows the pool: (re)built at the first dispatch after a pool change.  Every pool mutator has
@@ -1049,10 +1007,7 @@ static int launch_frame(svo_ctx *c, const Target &t, bool count) {
   if (rc) return rc;
   if (f.ntiles <= 0) return SVO_OK;
   int beam_set = -1;
-  if (c->use_beam) {
-    rc = launch_beam(c, t, f, beam_set);
-    if (rc) return rc;
-  }
+  if (c->use_beam) HIPCHK(c, beam::enqueue(c->beam, c->d_pool, c->pool_len, f, t.stream, beam_set));
   const int nb = count ? 1 : t.batch;
   if (nb > 1 && !t.external)
     return fail(c, SVO_E_INVALID, "svo_set_batch: a batch renders into caller-owned outputs (svo_bind_outputs)");
@@ -1099,10 +1054,7 @@ static int launch_frame(svo_ctx *c, const Target &t, bool count) {
       rc = launch_frame_kernels(c, t, g, count, o.color + at, o.depth + at, o.hits ? o.hits + at : nullptr);
     }
   }
-  if (rc == SVO_OK && beam_set >= 0) {
-    HIPCHK(c, hipEventRecord(c->beam_done[beam_set], t.stream));
-    c->beam_used[beam_set] = true;
-  }
+  if (rc == SVO_OK && beam_set >= 0) HIPCHK(c, beam::record(c->beam, beam_set, t.stream));
   return rc;
 }
 
@@ -1142,82 +1094,45 @@ static int launch_frame_kernels(svo_ctx *c, const Target &t, Frame &f, bool coun
   return SVO_OK;
 }
 
-// The frame's pick: a launch of ONE wave (pick_kernel, svo_fused.hip.h) on a high-priority stream of its own, in front of the
-// frame's kernels; a mail slot of its own per dispatch (kPickSlots of them, round-robin).  Frames the live shader's store
-// applies to: one sample per pixel, no cross-frame accumulation, no batch, no beam pre-pass (its start distances change the
+// The frame's pick: a launch of ONE wave on a high-priority stream of its own (pick::launch, svo_fused.hip.h), in front of the
+// frame's kernels.  Which frames get one is decided here: those the live shader's store applies to: one sample per pixel, no cross-frame accumulation, no batch, no beam pre-pass (its start distances change the
 // iteration count of the hit record), the whole frame (a rank's stripes / a row band may not even contain the pixel).
 static int launch_pick(svo_ctx *c, const Target &t) {
-  c->pick_live = false;
-  if (c->pick_x < 0 || t.batch != 1 || c->progressive || c->spp != 1 || c->use_beam || c->rows_set || c->n_tile_rows >= 0) return SVO_OK;
+  c->pick.invalidate();
+  if (c->pick.x < 0 || t.batch != 1 || c->progressive || c->spp != 1 || c->use_beam || c->rows_set || c->n_tile_rows >= 0) return SVO_OK;
   Frame f;
   int rc = make_frame(c, t, f);
   if (rc) return rc;
-  if (f.ntiles <= 0 || c->pick_x >= f.width || c->pick_y >= f.height) return SVO_OK;
-  // (the pick is a convenience: a runtime that cannot give it its mail or its stream leaves every read-back on the waiting path)
-  if (!c->pick_mail) {
-    if (hipHostMalloc((void **)&c->pick_mail, (size_t)kPickSlots * kPickWords * sizeof(uint32_t), hipHostMallocCoherent) != hipSuccess) {
-      c->pick_mail = nullptr;
-      (void)hipGetLastError();
-      return SVO_OK;
-    }
-    memset(c->pick_mail, 0, (size_t)kPickSlots * kPickWords * sizeof(uint32_t));
-  }
-  if (!c->pick_stream) {
-    int lo = 0, hi = 0;   // (hi = the greatest priority = the numerically lowest value)
-    if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) hi = 0;
-    if (hipStreamCreateWithPriority(&c->pick_stream, hipStreamNonBlocking, hi) != hipSuccess &&
-        hipStreamCreateWithFlags(&c->pick_stream, hipStreamNonBlocking) != hipSuccess) {
-      c->pick_stream = nullptr;
-      (void)hipGetLastError();
-      return SVO_OK;
-    }
-  }
-  const uint32_t seq = c->pick_seq + 1u == 0u ? 1u : c->pick_seq + 1u;   // (0 = "nothing written yet")
-  uint32_t *mail = c->pick_mail + (size_t)(seq % (uint32_t)kPickSlots) * kPickWords;
-  hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(64), 0, c->pick_stream, c->d_pool, f, c->pick_x, c->pick_y, mail, seq);
-  HIPCHK(c, hipGetLastError());
-  c->pick_seq = seq;
-  c->pick_live = true; c->pick_live_x = c->pick_x; c->pick_live_y = c->pick_y;
+  if (f.ntiles <= 0 || c->pick.x >= f.width || c->pick.y >= f.height) return SVO_OK;
+  HIPCHK(c, pick::launch(c->pick, c->d_pool, f));
   return SVO_OK;
 }
 
 int svo_dispatch_async(svo_ctx *c) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  // Up to kMaxSets (8) sets {stream, images} in turn while the library owns them and nothing ties a frame to the image before it: the
+  // Up to ImageSets::kMax (8) sets {stream, images} in turn while the library owns them and nothing ties a frame to the image before it: the
   // next frame's persistent waves take the CUs this frame's tail frees (glDispatchCompute only enqueues as well: Renderer.java:118-121).
-  const bool own = !c->external_outputs && c->sets[0].color && c->is_own_stream(c->stream);
-  const bool overlapped = c->overlap > 1 && own && c->pipeline == 1 && !c->progressive && c->batch == 1;
+  ImageSets &sets = c->sets;
+  const bool own = !c->external_outputs && sets[0].color && sets.is_own_stream(c->stream);
+  const bool overlapped = sets.overlap > 1 && own && c->pipeline == 1 && !c->progressive && c->batch == 1;
   if (overlapped) {
-    const int k = (c->cur_set + 1) % c->overlap;
-    ImageSet &s = c->sets[k];
-    // nothing of the context names set k before it is whole: a failed step leaves cur_set, c->stream and c->d_* as they were, and the
-    // next call tries again
-    if (!s.stream) HIPCHK(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    if (!s.color) {
-      const size_t n = (size_t)c->width * (size_t)c->height;
-      HIPCHK(c, alloc_planes(n, true, s));
-      HIPCHK(c, hipMemsetAsync(s.color, 0, n * 4, s.stream));
-      HIPCHK(c, hipMemsetAsync(s.depth, 0, n * 4, s.stream));
-      HIPCHK(c, hipMemsetAsync(s.hits, 0, n * 16, s.stream));
-    }
-    // the host runs ahead of the GPU by at most `overlap` frames (a swap chain's depth): the set's previous frame must be complete
-    // (the pick launches do not throttle it any more: they need a wave slot, not the frame's turn)
-    if (!s.done) HIPCHK(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    if (s.used) HIPCHK(c, hipEventSynchronize(s.done));
-    c->cur_set = k; c->stream = s.stream;
+    // nothing of the context names the next set before it is whole: a failed step leaves the current set, c->stream and c->d_* as
+    // they were
+    HIPCHK(c, sets.take_next((size_t)c->width * (size_t)c->height));
+    const ImageSet &s = sets.current();
+    c->stream = s.stream;
     c->d_color = s.color; c->d_depth = s.depth; c->d_hits = s.hits;
-    c->others_inflight = true;
   }
   Target t = current_target(c);
-  if (overlapped) { t.shape = kOverlap; t.overlap_sets = c->overlap; }   // the launch shape of overlapping one-frame launches
+  if (overlapped) { t.shape = kOverlap; t.overlap_sets = sets.overlap; }   // the launch shape of overlapping one-frame launches
   int rc = launch_pick(c, t);
   if (rc == SVO_OK) {
     rc = launch_frame(c, t, false);
-    if (rc) c->pick_live = false;
+    if (rc) c->pick.invalidate();
   }
   if (overlapped && rc == SVO_OK) {
-    ImageSet &s = c->sets[c->cur_set];
+    ImageSet &s = sets.current();
     HIPCHK(c, hipEventRecord(s.done, s.stream));
     s.used = true;
   }
@@ -1228,7 +1143,7 @@ int svo_sync(svo_ctx *c) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->others_inflight) return sync_own_streams(c);   // the other sets' frames too
+  if (c->sets.others_inflight) HIPCHK(c, c->sets.sync_own_streams());   // the other sets' frames too
   return SVO_OK;
 }
 
@@ -1240,7 +1155,7 @@ int svo_dispatch(svo_ctx *c) {
   int rc = launch_pick(c, t);
   if (rc) return rc;
   rc = launch_frame(c, t, false);
-  if (rc) { c->pick_live = false; return rc; }
+  if (rc) { c->pick.invalidate(); return rc; }
   HIPCHK(c, hipEventRecord(c->ev1, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0;
@@ -1252,7 +1167,7 @@ int svo_dispatch(svo_ctx *c) {
 int svo_count_frame(svo_ctx *c, svo_stats *out) {
   if (!c) return SVO_E_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
-  c->pick_live = false;   // (the counting pass renders into the current images)
+  c->pick.invalidate();   // (the counting pass renders into the current images)
   int rc = launch_frame(c, current_target(c), true);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1273,7 +1188,7 @@ int svo_get_stats(svo_ctx *c, svo_stats *out) {
 int svo_time_frames(svo_ctx *c, int warmup, int iters, float *ms) {
   if (!c || iters <= 0 || !ms) return fail(c, SVO_E_INVALID, "svo_time_frames: bad arguments");
   HIPCHK(c, hipSetDevice(c->device));
-  c->pick_live = false;
+  c->pick.invalidate();
   std::vector<hipEvent_t> ev((size_t)iters + 1, nullptr);
   const Target t = current_target(c);
   int rc = SVO_OK;
@@ -1369,293 +1284,11 @@ int svo_cast_info(svo_ctx *c, uint64_t *calls, uint64_t *rays_, int *waves, int 
   return SVO_OK;
 }
 
-// ---------------------------------------------------------------- frames in flight behind the boundary
-static int ring_create_impl(svo_ctx *c, int slots, int frames_per_slot, int want_hits, bool own_images);
-int svo_ring_create(svo_ctx *c, int slots, int frames_per_slot, int want_hits) {
-  return ring_create_impl(c, slots, frames_per_slot, want_hits, true);
-}
-// own_images = false: every slot will be bound to caller-owned buffers before its first submission (svo_group_*)
-static int ring_create_impl(svo_ctx *c, int slots, int frames_per_slot, int want_hits, bool own_images) {
-  if (!c || slots < 1 || slots > 8 || frames_per_slot < 1 || frames_per_slot > 64)
-    return fail(c, SVO_E_INVALID, "svo_ring_create: 1..8 slots of 1..64 frames");
-  if (c->width <= 0 || c->height <= 0) return fail(c, SVO_E_INVALID, "svo_ring_create: svo_resize not called");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
-  ring_free(c);
-  const uint64_t stride = (uint64_t)c->width * (uint64_t)c->height;
-  if (stride * (uint64_t)frames_per_slot >= (1ull << 32)) return fail(c, SVO_E_INVALID, "svo_ring_create: slot too large for 32-bit output indices");
-  c->ring.resize((size_t)slots);
-  const size_t n = (size_t)stride * (size_t)frames_per_slot;
-  // CU mask of the slots' streams: bit i = CU i / 8 of XCD i % 8 (tools/cumask_probe.hip); the top 8 r bits cleared
-  // keep r CUs of every XCD free of persistent waves
-  int ncu = 256;
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-  std::vector<uint32_t> cumask((size_t)(ncu + 31) / 32, 0xffffffffu);
-  const int reserve = std::min(c->reserved_cus * 8, ncu - 8);
-  for (int b = ncu - reserve; b < ncu && reserve > 0; b++) cumask[(size_t)b >> 5] &= ~(1u << (b & 31));
-  if (ncu & 31) cumask.back() &= (1u << (ncu & 31)) - 1u;
-  c->pb.set.cus_reserved = reserve > 0 ? reserve : 0;
-  for (auto &s : c->ring) {
-    hipError_t e = reserve > 0 ? hipExtStreamCreateWithCUMask(&s.stream, (uint32_t)cumask.size(), cumask.data())
-                               : hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&s.e0);
-    if (e == hipSuccess) e = hipEventCreate(&s.e1);
-    if (e == hipSuccess && own_images) e = alloc_planes(n, want_hits != 0, s);
-    if (e == hipSuccess && own_images) e = hipMemset(s.color, 0, n * 4);
-    if (e == hipSuccess && own_images) e = hipMemset(s.depth, 0, n * 4);
-    if (e == hipSuccess && own_images && want_hits) e = hipMemset(s.hits, 0, n * 16);
-    if (e != hipSuccess) {
-      ring_free(c);
-      return fail(c, SVO_E_HIP, std::string("svo_ring_create: ") + hipGetErrorString(e));
-    }
-  }
-  HIPCHK(c, hipDeviceSynchronize());   // the zeroing above is asynchronous; the slots' streams do not wait for the null stream
-  c->ring_frames = frames_per_slot;
-  c->ring_stride = stride;
-  return SVO_OK;
-}
-
-int svo_set_reserved_cus(svo_ctx *c, int per_xcd) {
-  if (!c || per_xcd < 0 || per_xcd > 16) return fail(c, SVO_E_INVALID, "svo_set_reserved_cus: 0..16 CUs per XCD");
-  c->reserved_cus = per_xcd;
-  return SVO_OK;
-}
-
-int svo_ring_destroy(svo_ctx *c) {
-  if (!c) return SVO_E_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipDeviceSynchronize());
-  ring_free(c);
-  return SVO_OK;
-}
-
-static svo_ctx::RingSlot *ring_slot(svo_ctx *c, int slot, const char *who) {
-  if (!c) return nullptr;
-  if (slot < 0 || slot >= (int)c->ring.size()) {
-    (void)fail(c, SVO_E_INVALID, std::string(who) + ": no such slot (svo_ring_create first)");
-    return nullptr;
-  }
-  return &c->ring[(size_t)slot];
-}
-
-int svo_ring_bind_slot(svo_ctx *c, int slot, void *color, void *depth, void *hits, uint64_t frame_stride) {
-  svo_ctx::RingSlot *s = ring_slot(c, slot, "svo_ring_bind_slot");
-  if (!s) return SVO_E_INVALID;
-  if (color && (!depth || frame_stride == 0)) return fail(c, SVO_E_INVALID, "svo_ring_bind_slot: depth buffer and frame stride required");
-  if (color && frame_stride * (uint64_t)c->ring_frames >= (1ull << 32)) return fail(c, SVO_E_INVALID, "svo_ring_bind_slot: slot too large for 32-bit output indices");
-  s->xcolor = color; s->xdepth = color ? depth : nullptr; s->xhits = color ? hits : nullptr; s->xstride = color ? frame_stride : 0;
-  return SVO_OK;
-}
-
-// The staged host-to-device copy of a submission's per-frame cameras, on the slot's stream, out of a pinned copy that is
-// rewritten only once the copy that last read it has run.  Called by persist_launch for launches whose cameras do not travel in
-// the table kernel's arguments.  Returns a hipError_t as int.
-static int ring_copy_cams(void *target) {
-  const Target *t = (const Target *)target;   // (the slot, the host cameras and their count)
-  svo_ctx::RingSlot *s = t->cams_slot;
-  if (!s || !t->cams || !s->d_fvar) return (int)hipErrorInvalidValue;
-  hipError_t e = hipEventSynchronize(s->fvar_copied);
-  if (e != hipSuccess) return (int)e;
-  memcpy(s->h_fvar, t->cams, (size_t)t->batch * sizeof(FrameVar));
-  e = hipMemcpyAsync(s->d_fvar, s->h_fvar, (size_t)t->batch * sizeof(FrameVar), hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess) e = hipEventRecord(s->fvar_copied, s->stream);
-  return (int)e;
-}
-
-// `cams`: null = nframes consecutive frames of the context's camera starting at frame_number (svo_ring_submit); else nframes
-// entries, every frame with its own camera and frameNumber (svo_ring_submit_cams)
-static int ring_submit(svo_ctx *c, int frame_number, int nframes, const FrameVar *cams, int *slot, const char *who) {
-  if (!c) return SVO_E_INVALID;
-  if (c->ring.empty()) return fail(c, SVO_E_INVALID, std::string(who) + ": svo_ring_create first");
-  if (nframes < 1 || nframes > c->ring_frames) return fail(c, SVO_E_INVALID, std::string(who) + ": 1..frames_per_slot frames");
-  // the cross-frame accumulation blends with what the previous dispatch left in the SAME image (svotrace.comp:712-719); a
-  // ring of several slots hands every submission another image, so a continued accumulation would blend with the frame of
-  // `slots` submissions ago.  Sequences that start on a fresh image (svo_set_sequence(n, 1)) are whole in one slot.
-  if (c->progressive && !c->seq_fresh && c->ring.size() > 1)
-    return fail(c, SVO_E_INVALID, std::string(who) + ": a progressive accumulation that continues on the previous image needs a ring of "
-                                  "ONE slot (or svo_dispatch); with several slots start every submission fresh: svo_set_sequence(n, 1)");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int si = (int)(c->ring_next % (unsigned)c->ring.size());
-  svo_ctx::RingSlot &s = c->ring[(size_t)si];
-  if (!s.xcolor && !s.color) return fail(c, SVO_E_INVALID, std::string(who) + ": the slot has no images (bind it first)");
-  // the launch's target: this slot's stream, images and frame range; the context's own dispatch state is not touched
-  Target t;
-  t.stream = s.stream; t.external = true; t.batch = nframes; t.frame_number = frame_number;
-  if (s.xcolor) { t.out.color = (uint32_t *)s.xcolor; t.out.depth = (float *)s.xdepth; t.out.hits = (uint4 *)s.xhits; t.frame_stride = s.xstride; }
-  else { t.out = s; t.frame_stride = c->ring_stride; }
-  memcpy(t.cam, c->cam, sizeof t.cam);
-  // the launch shape a ring of several slots gets unless svo_set_tuning named one: kRingWavesPerCu persistent waves per CU
-  if (c->ring.size() > 1) t.shape = kRing;
-  int rc = SVO_OK;
-  hipError_t e = hipSuccess;
-  if (cams && nframes == 1) {           // one frame: simply this frame's camera (beam pre-pass and all)
-    memcpy(t.cam, cams[0].cam, sizeof t.cam);
-    t.frame_number = cams[0].frame_number;
-  } else if (cams) {
-    // the batch's cameras live in the slot's table on the device.  Launches with row / column tables carry them there inside the
-    // table kernel's arguments (up to kCamPack frames); the others get the staged copy of ring_copy_cams, enqueued by the
-    // launch itself in front of the first kernel that reads the table.
-    if (!s.d_fvar) {
-      e = hipMalloc((void **)&s.d_fvar, (size_t)c->ring_frames * sizeof(FrameVar));
-      if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_fvar, (size_t)c->ring_frames * sizeof(FrameVar), hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&s.fvar_copied, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventRecord(s.fvar_copied, s.stream);   // (so that the first wait below has something to wait for)
-    }
-    t.cams = cams; t.cams_slot = &s;
-    t.frame_number = cams[0].frame_number;
-  }
-  if (e == hipSuccess) e = hipEventRecord(s.e0, s.stream);
-  if (e == hipSuccess) rc = launch_frame(c, t, false);
-  if (e == hipSuccess && rc == SVO_OK) e = hipEventRecord(s.e1, s.stream);
-  if (e == hipSuccess && rc == SVO_OK && s.fwd_dst) {
-    // the slot's frames travel to the frame owner behind the launch, on the same stream: a device-to-device copy (SDMA
-    // between GPUs: no CU slot needed next to the persistent waves), then the submission's number into the owner's flag
-    if (s.fwd_dst_device >= 0 && s.fwd_dst_device != c->device)
-      e = hipMemcpyPeerAsync(s.fwd_dst, s.fwd_dst_device, s.fwd_src, c->device, s.fwd_bytes, s.stream);
-    else
-      e = hipMemcpyAsync(s.fwd_dst, s.fwd_src, s.fwd_bytes, hipMemcpyDeviceToDevice, s.stream);
-    if (e == hipSuccess && s.fwd_flag) {
-      e = hipMemsetD32Async((hipDeviceptr_t)s.seq_word, (int)(c->ring_next + 1u), 1, s.stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(s.fwd_flag, s.seq_word, 4, hipMemcpyDeviceToDevice, s.stream);
-    }
-    if (e == hipSuccess && s.e2) e = hipEventRecord(s.e2, s.stream);
-  }
-  if (e != hipSuccess) return fail(c, SVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  if (rc) return rc;
-  s.first_frame = cams ? cams[0].frame_number : frame_number; s.nframes = nframes; s.used = true;
-  c->ring_next++;
-  if (slot) *slot = si;
-  return SVO_OK;
-}
-
-int svo_ring_submit(svo_ctx *c, int frame_number, int nframes, int *slot) {
-#if SVO_VARIANTS
-  static const bool force_cams = getenv("SVO_FORCE_CAMS") && atoi(getenv("SVO_FORCE_CAMS")) != 0;   // A/B: the kCams kernel on a static camera
-#else
-  const bool force_cams = false;
-#endif
-  if (force_cams && c && nframes > 1 && nframes <= 64 && !c->use_beam && !c->progressive) {
-    FrameVar v[64];
-    for (int k = 0; k < nframes; k++) { memcpy(v[k].cam, c->cam, sizeof v[k].cam); v[k].frame_number = frame_number + k; }
-    return ring_submit(c, frame_number, nframes, v, slot, "svo_ring_submit");
-  }
-  return ring_submit(c, frame_number, nframes, nullptr, slot, "svo_ring_submit");
-}
-
-int svo_ring_submit_cams(svo_ctx *c, int nframes, const float *cams, const int *frame_numbers, int *slot) {
-  if (!c || !cams || !frame_numbers) return fail(c, SVO_E_INVALID, "svo_ring_submit_cams: null array");
-  if (nframes < 1 || nframes > 64) return fail(c, SVO_E_INVALID, "svo_ring_submit_cams: 1..frames_per_slot frames");
-  FrameVar v[64];
-  for (int k = 0; k < nframes; k++) {
-    memcpy(v[k].cam, cams + 15 * (size_t)k, sizeof v[k].cam);
-    v[k].frame_number = frame_numbers[k];
-  }
-  return ring_submit(c, frame_numbers[0], nframes, v, slot, "svo_ring_submit_cams");
-}
-
-int svo_ring_wait(svo_ctx *c, int slot) {
-  svo_ctx::RingSlot *s = ring_slot(c, slot, "svo_ring_wait");
-  if (!s) return SVO_E_INVALID;
-  if (!s->used) return SVO_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(s->e1));
-  return SVO_OK;
-}
-
-int svo_ring_query(svo_ctx *c, int slot, int *done, int *first_frame, int *nframes, float *gpu_ms) {
-  svo_ctx::RingSlot *s = ring_slot(c, slot, "svo_ring_query");
-  if (!s) return SVO_E_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  bool fin = true;
-  if (s->used) {
-    const hipError_t q = hipEventQuery(s->e1);
-    if (q == hipErrorNotReady) fin = false;
-    else if (q != hipSuccess) return fail(c, SVO_E_HIP, std::string("svo_ring_query: ") + hipGetErrorString(q));
-  }
-  if (done) *done = fin ? 1 : 0;
-  if (first_frame) *first_frame = s->first_frame;
-  if (nframes) *nframes = s->used ? s->nframes : 0;
-  if (gpu_ms) {
-    *gpu_ms = 0.0f;
-    if (s->used && fin) HIPCHK(c, hipEventElapsedTime(gpu_ms, s->e0, s->e1));
-  }
-  return SVO_OK;
-}
-
-// frame k of a slot: base pointers of its three images
-static int ring_frame(svo_ctx *c, int slot, int k, const char *who, const uint32_t **col, const float **dep, const uint4 **hit,
-                      size_t *elems = nullptr) {
-  svo_ctx::RingSlot *s = ring_slot(c, slot, who);
-  if (!s) return SVO_E_INVALID;
-  if (!s->used || k < 0 || k >= s->nframes) return fail(c, SVO_E_INVALID, std::string(who) + ": the slot does not hold that frame");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(s->e1));
-  const uint64_t stride = s->xcolor ? s->xstride : c->ring_stride;
-  const uint64_t o = (uint64_t)k * stride;
-  // a caller-owned slot may hold less than W x H elements per frame (packed stripes of one rank)
-  if (elems) *elems = (size_t)std::min<uint64_t>((uint64_t)c->width * (uint64_t)c->height, stride);
-  *col = (s->xcolor ? (const uint32_t *)s->xcolor : s->color) + o;
-  *dep = (s->xcolor ? (const float *)s->xdepth : s->depth) + o;
-  const uint4 *h = s->xcolor ? (const uint4 *)s->xhits : s->hits;
-  *hit = h ? h + o : nullptr;
-  return SVO_OK;
-}
-
-int svo_ring_read_color(svo_ctx *c, int slot, int k, void *rgba8) {
-  const uint32_t *col; const float *dep; const uint4 *hit;
-  if (!rgba8) return fail(c, SVO_E_INVALID, "readback: null buffer");
-  size_t n = 0;
-  int rc = ring_frame(c, slot, k, "svo_ring_read_color", &col, &dep, &hit, &n);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpy(rgba8, col, n * 4, hipMemcpyDeviceToHost));
-  return SVO_OK;
-}
-int svo_ring_read_depth(svo_ctx *c, int slot, int k, float *depth) {
-  const uint32_t *col; const float *dep; const uint4 *hit;
-  if (!depth) return fail(c, SVO_E_INVALID, "readback: null buffer");
-  size_t n = 0;
-  int rc = ring_frame(c, slot, k, "svo_ring_read_depth", &col, &dep, &hit, &n);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpy(depth, dep, n * 4, hipMemcpyDeviceToHost));
-  return SVO_OK;
-}
-int svo_ring_read_hits(svo_ctx *c, int slot, int k, svo_hit *hits) {
-  const uint32_t *col; const float *dep; const uint4 *hit;
-  if (!hits) return fail(c, SVO_E_INVALID, "readback: null buffer");
-  size_t n = 0;
-  int rc = ring_frame(c, slot, k, "svo_ring_read_hits", &col, &dep, &hit, &n);
-  if (rc) return rc;
-  if (!hit) return fail(c, SVO_E_INVALID, "svo_ring_read_hits: the ring was created without hit records");
-  HIPCHK(c, hipMemcpy(hits, hit, n * 16, hipMemcpyDeviceToHost));
-  return SVO_OK;
-}
-int svo_ring_read_pixel(svo_ctx *c, int slot, int k, int x, int y, void *rgba8, float *depth, svo_hit *hit) {
-  const uint32_t *col; const float *dep; const uint4 *hp;
-  if (!c) return SVO_E_INVALID;
-  if (x < 0 || y < 0 || x >= c->width || y >= c->height) return fail(c, SVO_E_INVALID, "svo_ring_read_pixel: outside the image");
-  int rc = ring_frame(c, slot, k, "svo_ring_read_pixel", &col, &dep, &hp);
-  if (rc) return rc;
-  const size_t o = (size_t)y * (size_t)c->width + (size_t)x;
-  if (rgba8) HIPCHK(c, hipMemcpy(rgba8, col + o, 4, hipMemcpyDeviceToHost));
-  if (depth) HIPCHK(c, hipMemcpy(depth, dep + o, 4, hipMemcpyDeviceToHost));
-  if (hit) {
-    if (!hp) return fail(c, SVO_E_INVALID, "svo_ring_read_pixel: the ring was created without hit records");
-    HIPCHK(c, hipMemcpy(hit, hp + o, 16, hipMemcpyDeviceToHost));
-  }
-  return SVO_OK;
-}
-
-int svo_ring_forward_slot(svo_ctx *c, int slot, const void *src, void *dst, uint64_t nbytes, void *flag) {
-  svo_ctx::RingSlot *s = ring_slot(c, slot, "svo_ring_forward_slot");
-  if (!s) return SVO_E_INVALID;
-  if (dst && (!src || nbytes == 0)) return fail(c, SVO_E_INVALID, "svo_ring_forward_slot: source and size required");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (dst && !s->seq_word) HIPCHK(c, hipMalloc((void **)&s->seq_word, 4));
-  if (dst && !s->e2) HIPCHK(c, hipEventCreateWithFlags(&s->e2, hipEventDisableTiming));
-  s->fwd_dst_device = -1;
-  s->fwd_src = dst ? src : nullptr; s->fwd_dst = dst; s->fwd_bytes = dst ? nbytes : 0; s->fwd_flag = dst ? flag : nullptr;
-  return SVO_OK;
-}
+}  // extern "C"
+// ---------------------------------------------------------------- frames in flight behind the boundary: the ring's functions
+#define SVO_RING_FUNCTIONS 1
+#include "svo_ring.hip.h"
+extern "C" {
 
 // ---------------------------------------------------------------- device memory shared between the ranks of one node
 int svo_dev_alloc(svo_ctx *c, uint64_t nbytes, void **dptr) {
@@ -1708,17 +1341,6 @@ int svo_ipc_close(svo_ctx *c, void *dptr) {
   return fail(c, SVO_E_INVALID, "svo_ipc_close: not opened by this context");
 }
 
-int svo_ring_device_ptrs(svo_ctx *c, int slot, void **color, void **depth, void **hits, uint64_t *frame_stride, void **stream) {
-  svo_ctx::RingSlot *s = ring_slot(c, slot, "svo_ring_device_ptrs");
-  if (!s) return SVO_E_INVALID;
-  if (color) *color = s->xcolor ? s->xcolor : (void *)s->color;
-  if (depth) *depth = s->xcolor ? s->xdepth : (void *)s->depth;
-  if (hits) *hits = s->xcolor ? s->xhits : (void *)s->hits;
-  if (frame_stride) *frame_stride = s->xcolor ? s->xstride : c->ring_stride;
-  if (stream) *stream = (void *)s->stream;
-  return SVO_OK;
-}
-
 // ---------------------------------------------------------------- readback
 static int read_rows(svo_ctx *c, void *dst, const void *src, size_t elem) {
   if (!dst) return fail(c, SVO_E_INVALID, "readback: null buffer");
@@ -1734,14 +1356,15 @@ int svo_read_hits(svo_ctx *c, svo_hit *hits) { return c ? read_rows(c, hits, c->
 
 int svo_read_beam(svo_ctx *c, float *beam) {
   if (!c || !beam) return fail(c, SVO_E_INVALID, "svo_read_beam: null buffer");
-  if (!c->beam_frames || !c->beam_cap) return fail(c, SVO_E_INVALID, "svo_read_beam: no frame was dispatched with use_beam");
+  const beam::State &b = c->beam;
+  if (!b.frames || !b.cap) return fail(c, SVO_E_INVALID, "svo_read_beam: no frame was dispatched with use_beam");
   HIPCHK(c, hipSetDevice(c->device));
-  const int set = (int)((c->beam_frames - 1) % svo_ctx::kBeamSets);
+  const int set = (int)((b.frames - 1) % beam::kSets);
   // the frame that made this image may have run on another stream than the current one (frames in flight)
-  if (c->beam_used[set]) HIPCHK(c, hipEventSynchronize(c->beam_done[set]));
+  if (b.used[set]) HIPCHK(c, hipEventSynchronize(b.done[set]));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t n = (size_t)((c->width + kBeamBlock - 1) / kBeamBlock) * (size_t)((c->height + kBeamBlock - 1) / kBeamBlock);
-  HIPCHK(c, hipMemcpy(beam, c->d_beam[set], std::min(n, c->beam_cap) * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(beam, b.img[set], std::min(n, b.cap) * sizeof(float), hipMemcpyDeviceToHost));
   return SVO_OK;
 }
 
@@ -1750,31 +1373,16 @@ int svo_read_pixel(svo_ctx *c, int x, int y, void *rgba8, float *depth, svo_hit 
   if (x < 0 || y < 0 || x >= c->width || y >= c->height) return fail(c, SVO_E_INVALID, "svo_read_pixel: outside the image");
   if (!c->d_color) return fail(c, SVO_E_INVALID, "readback before svo_resize");
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->pick_live && x == c->pick_live_x && y == c->pick_live_y && c->pick_mail && (!hit || (c->write_hits && c->d_hits))) {
-    // the pick pixel of the last dispatch: its pick launch has written (or will write) the mail slot -- no wait for the frame,
-    // no copy.  Should the pick stream run dry without the word, the waiting path answers.
-    volatile uint32_t *m = c->pick_mail + (size_t)(c->pick_seq % (uint32_t)kPickSlots) * kPickWords;
+  pick::State &p = c->pick;
+  if (p.live && x == p.live_x && y == p.live_y && p.mail && (!hit || (c->write_hits && c->d_hits))) {
+    // the pick pixel of the last dispatch: answered from its mail slot.  Should the pick stream run dry without the word, the
+    // waiting path answers.
     bool got = false;
-    for (unsigned spin = 0;; spin++) {
-      if (__atomic_load_n((const uint32_t *)m, __ATOMIC_ACQUIRE) == c->pick_seq) { got = true; break; }
-      if ((spin & 255u) == 255u) {
-        const hipError_t q = hipStreamQuery(c->pick_stream);
-        if (q == hipSuccess) { got = __atomic_load_n((const uint32_t *)m, __ATOMIC_ACQUIRE) == c->pick_seq; break; }
-        if (q != hipErrorNotReady) return fail(c, SVO_E_HIP, std::string("svo_read_pixel: ") + hipGetErrorString(q));
-      }
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-    if (got) {
-      c->pick_from_mail++;
-      if (rgba8) { const uint32_t v = m[1]; memcpy(rgba8, &v, 4); }
-      if (depth) { const uint32_t v = m[2]; memcpy(depth, &v, 4); }
-      if (hit) { uint32_t h[4] = {m[4], m[5], m[6], m[7]}; memcpy(hit, h, 16); }
-      return SVO_OK;
-    }
+    const hipError_t q = pick::poll(p, got, rgba8, depth, hit);
+    if (q != hipSuccess) return fail(c, SVO_E_HIP, std::string("svo_read_pixel: ") + hipGetErrorString(q));
+    if (got) return SVO_OK;
   }
-  c->pick_waited++;
+  p.waited++;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t o = (size_t)y * (size_t)c->width + (size_t)x;
   if (rgba8) HIPCHK(c, hipMemcpy(rgba8, c->d_color + o, 4, hipMemcpyDeviceToHost));

@@ -21,6 +21,7 @@
 // any pixel.
 #pragma once
 #include "svo_fused.hip.h"
+#include "svo_grow.h"
 #include "svo_persist_plan.h"
 #include "svo_trav.h"
 #include "svo_travloop.h"
@@ -1112,28 +1113,11 @@ inline void persist_free(PersistBuffers &b) {
   b = PersistBuffers();
 }
 
-// Grows a family of equally sized device buffers to `bytes` each: nothing in flight may still use the old ones, so the device is
-// waited for; then all are freed, `have` (and their in-use flags, if they have any) cleared, and all allocated anew.  `have`
-// becomes `want` only behind the last allocation: a failed grow leaves nothing half-sized, and the next launch grows again.
-template <class T, size_t N>
-inline hipError_t grow_device_buffers(T *(&bufs)[N], bool *used, size_t &have, size_t want, size_t bytes) {
-  hipError_t e;
-  if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
-  for (size_t i = 0; i < N; i++) {
-    if (bufs[i]) (void)hipFree(bufs[i]);
-    bufs[i] = nullptr;
-    if (used) used[i] = false;
-  }
-  have = 0;
-  for (size_t i = 0; i < N; i++)
-    if ((e = hipMalloc((void **)&bufs[i], bytes)) != hipSuccess) return e;
-  have = want;
-  return hipSuccess;
-}
-
 // the cache describes nothing any more (the pool changed, the host opted out).  The buffer and what is known about the launches
 // still using it stay: the next fill waits its turn like any other.
 inline void persist_kept_drop(PersistBuffers &b) { b.kept_valid = false; }
+// the pool's contents change: the epoch is part of the cache's key, and the cache is empty from here on
+inline void persist_pool_changed(PersistState &p) { p.set.pool_epoch++; persist_kept_drop(p.buf); }
 
 // has `ev` completed?  Never waits; hipErrorNotReady is no error and does not stay behind as one.
 inline bool persist_event_done(hipEvent_t ev) {

@@ -195,8 +195,8 @@ int svo_set_primary_cache(svo_ctx *ctx, int enabled);
 int svo_primary_cache_info(svo_ctx *ctx, uint64_t *fills, uint64_t *reuses, uint64_t *bytes, int *state);
 /* A submission that reads the cache and whose paths are primary + one bounce (bounces == 2, any mirror mask) shades every
  * (pixel, frame) in a dense kernel ahead of the walk and casts the prepared rays; longer paths shade in the walk as before.  Same
- * bytes.  Cost: 20 bytes of device memory per pixel and frame of the batch in each of the library's 8 launch slots (1080p x 4
- * frames: 166 MB each, 1.33 GB), allocated with the cache at its fill and freed by svo_resize / svo_destroy; when the allocation
+ * bytes.  Cost: 24 bytes of device memory per pixel and frame of the batch in each of the library's 8 launch slots (1080p x 4
+ * frames: 199 MB each, 1.59 GB), allocated with the cache at its fill and freed by svo_resize / svo_destroy; when the allocation
  * fails the submissions shade in the walk, without an error.  *launches = launches that took the dense pass since the context
  * was made, *bytes = device memory their ray records hold.  Either may be NULL.  Never waits. */
 int svo_dense_shade_info(svo_ctx *ctx, uint64_t *launches, uint64_t *bytes);

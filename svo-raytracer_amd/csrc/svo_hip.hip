@@ -801,7 +801,7 @@ int svo_primary_cache_info(svo_ctx *c, uint64_t *fills, uint64_t *reuses, uint64
 int svo_dense_shade_info(svo_ctx *c, uint64_t *launches, uint64_t *bytes) {
   if (!c) return SVO_E_INVALID;
   if (launches) *launches = c->pb.set.dense_launches;
-  if (bytes) *bytes = (uint64_t)c->pb.buf.ray_records * kRayBytes * kHeadSets;
+  if (bytes) *bytes = (uint64_t)c->pb.buf.ray_records * ray_record_bytes(c->pb.set.list_mode != 0) * kHeadSets;
   return SVO_OK;
 }
 

@@ -24,6 +24,10 @@ constexpr int kRingWavesPerCu = 10;
 // (profiles/round6_experiments.txt: 2 sets 12, 3 sets 10, 4 sets 8, 5 and more 6)
 inline int overlap_waves_per_cu(int sets) { return sets <= 2 ? 12 : sets == 3 ? 10 : sets == 4 ? 8 : 6; }
 
+// PersistSettings::list_mode of a new context
+#ifndef SVO_RAY_LIST
+#define SVO_RAY_LIST 1
+#endif
 // the round threshold of the spare-ray kernel (variants/svo_persist2.hip.h), sixteenths
 #ifndef SVO_SPARE_THRESH
 #define SVO_SPARE_THRESH 13
@@ -48,6 +52,10 @@ struct PersistSettings {
   int dense_mode = 1;     // 1 = a launch that reads the cache and ends its paths with the bounce shades every (pixel, frame) in a dense
                           // pass and casts the prepared rays (bounce_rays_kernel + persist_cast_kernel); environment
                           // SVO_DENSE_SHADE=0: persist_kept_kernel<false> shades in its rounds
+  int list_mode = SVO_RAY_LIST;   // 1 = the dense pass leaves a compact list of the rays to cast and the cast kernel draws runs of its
+                          // entries (ray_list_kernel + persist_runs_kernel); 0 = a record per (frame, pixel), a slot per pixel
+                          // (bounce_rays_kernel + persist_cast_kernel: the pass as it was first built, kept as the comparator).
+                          // On: -6.5 % on the headline (profiles/ray_list.md).  Environment SVO_RAY_LIST in the variants build
   int cus_reserved = 0;   // CUs the launching stream may not use (svo_set_reserved_cus): fewer persistent waves
   uint64_t pool_epoch = 0;   // bumped by everything that changes the pool (svo_hip.hip::pool_changed)
   uint64_t kept_fills = 0, kept_reuses = 0;
@@ -169,6 +177,71 @@ __attribute__((always_inline)) inline SlotPixel slot_pixel(const Frame &f, const
   return p;
 }
 
+// ---------------- the ray list of the dense pass (PersistPlan::list: ray_list_kernel -> persist_runs_kernel, svo_persistent.hip.h), its pure half.
+// The ray records of a launch are a compact list per band: only the (pixel, frame)s that cast a ray have an entry, in no
+// particular order: a tile's wave appends its entries where the band's fill count stands.
+// A record = {direction.xyz, rgba8 on a miss} in a 16-byte plane and {rgba8 on a hit, cache index | frame << kRayIndexBits} in an
+// 8-byte plane: the cast kernel takes the output index and the origin (the kept hit's position) from the last word.
+constexpr size_t kRayBytes = 20;       // a ray record at [frame][pixel]: {direction, rgba8 of a miss} in a 16-byte plane, rgba8 of a hit in a 4-byte plane
+constexpr size_t kRayListBytes = 24;   // ... and an entry of the list
+inline size_t ray_record_bytes(bool list) { return list ? kRayListBytes : kRayBytes; }
+constexpr uint32_t kRayIndexBits = 24;                   // the pixel's index in the cache; the frame of the batch sits above it
+constexpr uint32_t kRayIndexMask = (1u << kRayIndexBits) - 1u;
+constexpr uint32_t kRayNoEntry = 0xffffffffu;            // no record's last word: a frame is below kRayMaxFrames
+constexpr int kRayMaxFrames = 255;
+// entries a wave of persist_runs_kernel reserves with one atomic on its band's draw cursor
+// (128 / 256 / 512: 0.3417 / 0.2824 / 0.2825 ms per step, profiles/ray_list.md)
+constexpr uint32_t kChunk = 256;
+
+// do a launch's cache indices and frames fit a record's last word?  (persist_plan: if not, a context that keeps lists takes no dense pass)
+inline bool ray_list_fits(size_t kept_records, int frames) {
+  return kept_records <= (size_t)(kRayIndexMask + 1u) && frames <= kRayMaxFrames;
+}
+
+// Band `band`'s region of the launch's ray records: it starts at the record offset of the band's first tile row and has room for
+// the band's pixels x frames.  The regions of the 8 bands tile tiles_y * 8 * width * frames records (PersistPlan::ray_records).
+struct RayRegion {
+  uint32_t first, room;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline RayRegion ray_region(uint32_t band, int rows_per_band, int tiles_y, int width, int frames) {
+  const Band b = band_of(band, rows_per_band, 1, tiles_y, 1, 1, true);
+  const uint32_t per_row = 8u * (uint32_t)width * (uint32_t)frames;   // records of one tile row
+  RayRegion r;
+  r.first = (b.rows > 0 ? (uint32_t)b.first_row : (uint32_t)tiles_y) * per_row;
+  r.room = (uint32_t)b.rows * per_row;
+  return r;
+}
+
+// The draw of persist_runs_kernel: a wave holds a run [cur, end) of its band's entries.  ray_run_reserve: what one atomicAdd of kChunk
+// on the band's draw cursor (`base` = its return) gives a wave when the band holds `fill` entries; `last`: nothing of the band is
+// left behind this run, the wave goes on to the next band once it is used up.  ray_run_take: how many of `idle` lanes get an
+// entry (lane of rank r among the idle ones takes entry cur + r), and the run moves on.
+struct RayRun {
+  uint32_t cur, end;
+  bool last;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline RayRun ray_run_reserve(uint32_t base, uint32_t fill) {
+  RayRun r;
+  r.cur = base < fill ? base : fill;
+  r.end = base + kChunk < fill ? base + kChunk : fill;
+  r.last = base + kChunk >= fill;
+  return r;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+__attribute__((always_inline)) inline uint32_t ray_run_take(RayRun &r, uint32_t idle) {
+  const uint32_t left = r.end - r.cur, n = idle < left ? idle : left;
+  r.cur += n;
+  return n;
+}
+
 // can `n` samples (or frames of a progressive sequence) per pixel be carried by one launch of `f`?
 inline bool persist_can_fold(const Frame &f, int n, unsigned long long budget = kFoldBytes) {
   const unsigned long long nb = (unsigned long long)(f.batch > 1 ? f.batch : 1);
@@ -223,8 +296,8 @@ struct PersistPlan {
   // kernel.  (Longer paths shade their inner hits from the cast's result; every mirror mask is fine: scatter() takes it.)
   bool dense = false;
   size_t ray_records = 0;   // ray records the pass writes: one per (pixel of the launch's rows, frame of the batch) (0: no dense pass)
+  bool list = false;        // ... as a compact list, that room cut into the bands' regions (ray_region): PersistSettings::list_mode
 };
-constexpr size_t kRayBytes = 20;   // a ray record: {direction, rgba8 of a miss} in a 16-byte plane, rgba8 of a hit in a 4-byte plane
 
 // `out_npix` = elements of the output images: W*H, or more when packed stripes overhang the frame (caller-owned gather
 // buffers).  has_table: the launch walks the interior-descriptor table (else the records); has_cams: the frames of the batch
@@ -282,7 +355,10 @@ inline PersistPlan persist_plan(const PersistSettings &s, const PersistLimits &l
   // the primary-hit cache: static-camera batches without hit records (those would need a fourth plane), on the tables' kernels
   p.cache = p.span && s.kept_mode != 0 && f.write_hits == 0 && p.tables;
   if (p.cache) p.kept_records = (size_t)f.tiles_y * 8 * (size_t)f.width;
-  p.dense = p.cache && s.dense_mode != 0 && f.bounces == 2;
+  // (with lists: a launch whose cache indices or frames do not fit an entry's last word shades in its rounds, persist_kept_kernel<false>)
+  p.list = s.list_mode != 0;
+  p.dense = p.cache && s.dense_mode != 0 && f.bounces == 2 && (!p.list || ray_list_fits(p.kept_records, nb));
+  p.list = p.list && p.dense;
   if (p.dense) p.ray_records = p.kept_records * (size_t)nb;
   return p;
 }

@@ -52,7 +52,8 @@ struct PersistArgs {
   uint4 *hits;
   float *facc;       // spp > 1: colour sums (3 planes of npix)
   size_t npix;
-  uint32_t *heads;   // 8 band counters (pixel slots drawn so far)
+  uint32_t *heads;   // 8 band counters (pixel slots drawn so far; with a ray list: its entries drawn, and in word kFillWord of the band's
+                     // line the entries written)
   int tiles_per_band;  // unread since the row-major band walk went: kept, because without it hipcc allocates the kernels' registers differently
   int rows_per_band;   // tile rows per XCD band
   int reverse;         // walk the columns right to left (every other launch)
@@ -1039,6 +1040,163 @@ __global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_cast_k
   persist_cast_body(a, ra, stk);
 }
 
+// ---------------- the same pass with its ray records as a compact list (PersistPlan::list; ray_list_kernel + persist_runs_kernel)
+// The ray list of a launch (svo_persist_plan.h, "the ray list"): kRayListBytes per record in two planes, cut into the 8 bands'
+// regions (ray_region).  Only a (pixel, frame) that casts a ray has an entry: a pixel whose PRIMARY ray left the octree has its sky
+// stored by ray_list_kernel and appears nowhere.  Per band two words of its line in a.heads, both zeroed by rc_table_kernel: word 0
+// the draw cursor of persist_runs_kernel, word kFillWord the entries ray_list_kernel has written.
+struct RayListArgs {
+  uint4 *ray;   // {direction of the bounce ray, rgba8 should it miss}
+  uint2 *tag;   // {rgba8 should it hit, cache index | frame << kRayIndexBits}.  The hit's colour is not assumed black: a voxel with
+                // normal code 0 gives a NaN direction and NaN sums (quirk Q7)
+};
+constexpr uint32_t kFillWord = 1;
+
+// bounce_rays_kernel's shading with a thread per PIXEL of the launch's rows: a workgroup = one wave = an 8 x 8 tile, which lies in one
+// band; the thread loads the kept record once and shades the batch's frames one after the other -- the operations of
+// persist_reuse_body on a refilled lane, in its order.  A tile's pixels that hit are the same in every frame, so the wave reserves
+// room for all its entries with ONE atomic on the band's fill count (ballot + prefix count) and writes them frame by frame, each
+// frame's as one contiguous run.  The list is compacted, not ordered: a key on the ray's direction was measured and dropped
+// (profiles/ray_list.md).
+__global__ __launch_bounds__(64) void ray_list_kernel(const PersistArgs a, const RayListArgs ra) {
+  const Frame &f = a.f;
+  const uint32_t l = threadIdx.x, nb = (uint32_t)f.batch;
+  const int px = (int)(blockIdx.x * 8u + (l & 7u)), py = frame_gy(f, (int)blockIdx.y, (int)(l >> 3));
+  const uint32_t band = blockIdx.y / (uint32_t)a.rows_per_band;
+  const uint32_t idx = (uint32_t)frame_oy(f, (int)blockIdx.y, (int)(l >> 3)) * (uint32_t)f.width + (uint32_t)px - a.kept_origin;
+  bool live = false;
+  uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0, r2 = r0;
+  if (px < f.width && py < f.y1 && py < f.height) {
+    const uint4 *const rec = a.kept + idx;
+    r0 = rec[0]; r2 = rec[2u * a.kept_n];
+    if (r2.w == kKeptMiss) {   // the same sky in every frame, and no entry
+      const V3 s = sky_colour(mk(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z)));
+      for (uint32_t fi = 0; fi < nb; fi++)
+        persist_emit(a, idx + a.kept_origin + fi * f.frame_stride, 0u, px, py, mk(0.0f + s.x, 0.0f + s.y, 0.0f + s.z), 0.0f);
+    } else {
+      r1 = rec[a.kept_n];
+      live = true;
+    }
+  }
+  const unsigned long long m = __ballot(live);
+  if (m == 0ull) return;
+  const uint32_t n = (uint32_t)__builtin_popcountll(m);
+  const int leader = __builtin_ctzll(m);
+  uint32_t base = 0;
+  if ((int)l == leader) base = atomicAdd(a.heads + band * kHeadStride + kFillWord, n * nb);
+  base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+  if (!live) return;
+  // (at most the band's pixels x frames are ever reserved: the entry stays inside the band's region)
+  uint32_t e = ray_region(band, a.rows_per_band, f.tiles_y, f.width, f.batch).first + base +
+               __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  const V3 d = mk(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
+  const V3 hpos = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
+  const V3 hnormal = mk(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z));
+  for (uint32_t fi = 0; fi < nb; fi++, e += n) {
+    V3 mask = mk(1.f, 1.f, 1.f), accum = mk(0.f, 0.f, 0.f);
+    const float *fr = a.rc + (size_t)fi * a.rc_stride;
+    const float colx = fr[2 * px], roww = fr[((2 * f.width + 3) & ~3) + 8 * py + 3];
+    const float r = rand_of_dot(((float)px + colx) * 12.9898f + ((float)py + roww) * 78.233f);
+    bool sun_lit;
+    const V3 nd = shade_hit(f, d, hpos, hnormal, r1.w, r, mask, accum, sun_lit);
+    ra.ray[e] = make_uint4(__float_as_uint(nd.x), __float_as_uint(nd.y), __float_as_uint(nd.z), persist_rgba8(f, px, py, path_end(accum, mask, false, sun_lit)));
+    ra.tag[e] = make_uint2(persist_rgba8(f, px, py, path_end(accum, mask, true, sun_lit)), idx | (fi << kRayIndexBits));
+  }
+}
+
+// persist_cast_body without its pixels: the trips, thresh_num and the drain rule are the same, and so is the walk of the 8 bands (the
+// wave's XCD first, then stealing).  What a wave draws are ENTRIES of a band's ray list: it holds a wave-uniform run [cur, end) of
+// them, reserved kChunk at a time with one atomic on the band's draw cursor (ray_run_reserve), and idle lanes take the run's next
+// entries (ray_run_take), load their record and the origin (the kept hit's position, plane 1 of the cache) and cast.  A stopped lane
+// stores one of the record's two colour words and is idle: no lane keeps a pixel from frame to frame, no entry is empty.  Across
+// the trips a lane keeps its walk state, its output index and the two words.
+__device__ __forceinline__ void persist_runs_body(const PersistArgs &a, const RayListArgs &ra, DescWalk::Stack &stk) {
+  const uint32_t lane = threadIdx.x;
+  const Frame &f = a.f;
+  DescWalk walk;
+  walk.setup(a);
+
+  DescWalk::State t;
+  int status = ST_IDLE;
+  uint32_t pix = 0, miss_c = 0, hit_c = 0;
+
+  uint32_t band = xcc_id();
+  int bands_left = 8;
+  RayRun run;   // wave-uniform
+  run.cur = 0u; run.end = 0u; run.last = false;
+
+  for (;;) {
+    // ---------------- finished lanes store their pixel
+    if (status >= ST_HIT) {
+      const bool hit = status == ST_HIT;
+      a.color[pix] = hit ? hit_c : miss_c;
+      a.depth[pix] = hit ? walk.stop_t(t) : 0.0f;
+      status = ST_IDLE;
+    }
+
+    // ---------------- idle lanes take the next entries of the wave's run; a run used up is followed by the band's next one in the same
+    // round, a band used up by the next band in the next round (work stealing, as persist_body has it)
+    bool ninit = false;
+    V3 o = mk(0.f, 0.f, 0.f), d = mk(0.f, 0.f, 0.f);
+    while (bands_left > 0) {
+      const unsigned long long idle = __ballot(status == ST_IDLE);
+      if (idle == 0ull) break;
+      if (run.cur == run.end) {
+        if (run.last) {
+          band = (band + 1u) & 7u;
+          bands_left--;
+          run.last = false;
+          break;
+        }
+        const int leader = __builtin_ctzll(idle);
+        uint32_t base = 0, filled = 0;
+        if ((int)lane == leader) {
+          base = atomicAdd(a.heads + band * kHeadStride, kChunk);
+          filled = a.heads[band * kHeadStride + kFillWord];
+        }
+        run = ray_run_reserve((uint32_t)__builtin_amdgcn_readlane((int)base, leader), (uint32_t)__builtin_amdgcn_readlane((int)filled, leader));
+        continue;
+      }
+      const uint32_t at = run.cur;
+      const uint32_t n = ray_run_take(run, (uint32_t)__builtin_popcountll(idle));
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+      if (status == ST_IDLE && rank < n) {
+        const uint32_t e = ray_region(band, a.rows_per_band, f.tiles_y, f.width, f.batch).first + at + rank;
+        const uint4 q = ra.ray[e];
+        const uint2 w = ra.tag[e];
+        const uint32_t idx = w.y & kRayIndexMask;
+        const uint4 r1 = a.kept[a.kept_n + idx];
+        pix = idx + a.kept_origin + (w.y >> kRayIndexBits) * f.frame_stride;
+        miss_c = q.w;
+        hit_c = w.x;
+        o = mk(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
+        d = mk(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z));
+        ninit = true;
+        status = ST_ACTIVE;   // taken (the set-up below gives the real status)
+      }
+    }
+    // ---------------- set up the new rays
+    if (ninit) {
+      status = walk.init(t, o, d, true, 0.0f);
+      walk.fresh_stack(stk, lane);
+    }
+    if (__ballot(status != ST_IDLE) == 0ull) {
+      if (bands_left > 0) continue;
+      break;
+    }
+    // ---------------- traverse until enough lanes have stopped to make a round worthwhile (persist_body)
+    const int active0 = __builtin_popcountll(__ballot(status == ST_ACTIVE));
+    const int drained = (active0 * SVO_DRAIN_NUM) / 16 < active0 - 1 ? (active0 * SVO_DRAIN_NUM) / 16 : (active0 > 0 ? active0 - 1 : 0);
+    const int threshold = __builtin_amdgcn_readfirstlane(bands_left > 0 ? (active0 * a.thresh_num) / 16 : drained);
+    walk.run(stk, lane, t, status, __ballot(status == ST_ACTIVE), threshold, ~0ull, nullptr);
+  }
+}
+
+__global__ __launch_bounds__(64, WalkWaves<DescWalk>::value) void persist_runs_kernel(const PersistArgs a, const RayListArgs ra) {
+  __shared__ DescWalk::Stack stk;
+  persist_runs_body(a, ra, stk);
+}
+
 // a.fold > 1: tiles per group of a band's walk.  1 / 8 / 64 / 512 / all: 4.47 / 4.49 / 4.47 / 4.41 / 4.20 Grays/s at 64
 // samples per pixel (tools/history/r03_fold2.sh): a group's samples should be in flight together, not a whole band's
 constexpr int kFoldGroup = 8;
@@ -1084,7 +1242,7 @@ struct PersistBuffers {
   hipEvent_t kept_filled = nullptr;
   bool kept_reader[kHeadSets] = {};  // the set's head_done is behind a launch that read the cache (or behind one that waited for it)
   // the ray records of the dense pass (bounce_rays_kernel -> persist_cast_kernel), one buffer per counter set like the tables:
-  // kRayBytes x ray_records each, the 16-byte plane first
+  // ray_record_bytes() x ray_records each, the 16-byte plane first
   uint8_t *rays[kHeadSets] = {};
   size_t ray_records = 0;      // records each has room for
   size_t rays_failed = 0;      // ... and the size hipMalloc last refused: launches of that size and larger shade in persist_kept_kernel<false>
@@ -1344,6 +1502,7 @@ inline hipError_t persist_prepare(PersistState &p) {
     if (const char *e5 = getenv("SVO_NORMAL_TABLE")) s.ntab_mode = atoi(e5) != 0 ? 1 : 0;
     if (const char *e6 = getenv("SVO_BATCH_PRIMARY")) s.span_mode = atoi(e6) != 0 ? 1 : 0;
     if (const char *e7 = getenv("SVO_DENSE_SHADE")) s.dense_mode = atoi(e7) != 0 ? 1 : 0;
+    if (const char *e8 = getenv("SVO_RAY_LIST")) s.list_mode = atoi(e8) != 0 ? 1 : 0;
 #endif
   }
   return hipSuccess;
@@ -1397,14 +1556,15 @@ inline hipError_t persist_kept_launched(PersistState &p, const PersistArgs &a, i
 // is left is room for its ray records.  They grow with the FILL, next to the cache itself: the wait for the device and the
 // allocations (8 ms at 1080p x 4 frames) then fall on the submission that casts its primaries anyway, not on the first one that
 // could run without.  An allocation that fails is no error: launches of that size shade in their rounds as before.
-inline hipError_t persist_dense_choose(PersistState &p, const PersistPlan &plan, const PersistArgs &a, int hset, RayArgs &ra) {
+inline hipError_t persist_dense_choose(PersistState &p, const PersistPlan &plan, const PersistArgs &a, int hset, RayArgs &ra, RayListArgs &rl) {
   PersistBuffers &b = p.buf;
   ra.ray = nullptr; ra.hitc = nullptr; ra.n = 0;
+  rl.ray = nullptr; rl.tag = nullptr;
   if (!plan.dense || !a.kept) return hipSuccess;
   if (b.ray_records < plan.ray_records) {
     if (b.rays_failed != 0 && plan.ray_records >= b.rays_failed) return hipSuccess;
     // (launches in flight may still read the old records: grow_device_buffers waits for the device)
-    const hipError_t e = grow_device_buffers(b.rays, nullptr, b.ray_records, plan.ray_records, plan.ray_records * kRayBytes);
+    const hipError_t e = grow_device_buffers(b.rays, nullptr, b.ray_records, plan.ray_records, plan.ray_records * ray_record_bytes(p.set.list_mode != 0));
     if (e == hipErrorOutOfMemory) {
       (void)hipGetLastError();
       for (auto &r : b.rays) { if (r) (void)hipFree(r); r = nullptr; }
@@ -1414,6 +1574,11 @@ inline hipError_t persist_dense_choose(PersistState &p, const PersistPlan &plan,
     if (e != hipSuccess) return e;
   }
   if (a.kept_fill) return hipSuccess;
+  if (plan.list) {
+    rl.ray = (uint4 *)b.rays[hset];
+    rl.tag = (uint2 *)(b.rays[hset] + b.ray_records * sizeof(uint4));
+    return hipSuccess;
+  }
   ra.ray = (uint4 *)b.rays[hset];
   ra.hitc = (uint32_t *)(b.rays[hset] + b.ray_records * sizeof(uint4));
   ra.n = (uint32_t)plan.kept_records;
@@ -1512,7 +1677,8 @@ inline int persist_launch(PersistState &p, const Frame &f, const PersistLaunch &
   if (p.set.ntab_mode == 0) a.ntab = nullptr;
   if (plan.cache && (e = persist_kept_choose(p, in, f, plan.kept_records, a)) != hipSuccess) return (int)e;
   RayArgs ra;
-  if ((e = persist_dense_choose(p, plan, a, hset, ra)) != hipSuccess) return (int)e;
+  RayListArgs rl;
+  if ((e = persist_dense_choose(p, plan, a, hset, ra, rl)) != hipSuccess) return (int)e;
 
   if (b.head_used[hset] && (e = hipStreamWaitEvent(in.stream, b.head_done[hset], 0)) != hipSuccess) return (int)e;
   const int nb = f.batch > 1 ? f.batch : 1;
@@ -1532,6 +1698,14 @@ inline int persist_launch(PersistState &p, const Frame &f, const PersistLaunch &
       hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, in.stream, a.heads, (uint32_t)kHeadWords);
     }
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (rl.ray) {   // the same with the rays to cast as a list
+      hipLaunchKernelGGL(ray_list_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y), dim3(64), 0, in.stream, a, rl);
+      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(persist_runs_kernel, dim3((unsigned)plan.blocks), dim3(64), 0, in.stream, a, rl);
+      if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+      p.set.dense_launches++;
+      continue;
+    }
     if (ra.ray) {   // (mode 0, one launch: persist_plan) the tables -> every (pixel, frame)'s shading -> the casts
       hipLaunchKernelGGL(bounce_rays_kernel, dim3((unsigned)f.tiles_x, (unsigned)f.tiles_y, (unsigned)nb), dim3(64), 0, in.stream, a, ra);
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
